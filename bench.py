@@ -2,6 +2,7 @@
 """Headline benchmark: 512x512 4-step LCM images/sec on N MI355X (BASELINE.json metric).
 
   python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --dump-outputs DIR               (also write the last timed step's outputs as DIR/<name>.npy)
 
 A "step" is one pass of the hot path over one batch: a full 4-step LCM sample (4 x UNet + scheduler steps +
 VAE decode to RGB8) replayed from the captured hipGraph, inputs (prompt embeddings, per-request noise)
@@ -275,6 +276,34 @@ def worker_leg(n_clients=16, n_requests=128, lone_requests=24, keep_timing=False
                 os.environ[k] = v
 
 
+DUMP_BUDGET_BYTES = 64 << 20     # --dump-outputs: all arrays of all ranks together
+
+
+def dump_outputs(out_dir, arrays, budget_bytes, suffix=""):
+    """Write each array as out_dir/<name><suffix>.npy in float32 (float64 stays float64).  The arrays share budget_bytes:
+    one that does not fit its share is replaced by a fixed sample of its flattened values (indices drawn from a generator
+    seeded by the array's shape, sorted), so that two runs with the same arguments dump the same positions.
+    -> {name: {"shape", "dtype", "sampled"}} for the result line."""
+    import numpy as np
+    info = {}
+    left = budget_bytes - 4096 * len(arrays)            # room for the .npy headers
+    for k, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].size)):
+        a = np.ascontiguousarray(a)
+        dt = np.float64 if a.dtype == np.float64 else np.float32
+        share = left // (len(arrays) - k) // np.dtype(dt).itemsize
+        flat = a.reshape(-1).astype(dt)
+        sampled = None
+        if flat.size > share:
+            rng = np.random.default_rng([int(s) for s in a.shape])
+            flat = flat[np.sort(rng.choice(a.size, size=share, replace=False))]
+            sampled = int(share)
+        v = flat if sampled is not None else flat.reshape(a.shape)
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), v)
+        left -= v.nbytes
+        info[name] = {"shape": list(a.shape), "dtype": np.dtype(dt).name, "sampled": sampled}
+    return info
+
+
 def spawn_command(gpus, argv, env):
     """`python bench.py --gpus N` run by hand (no torchrun environment): the command that launches N fresh ranks, one per
     GPU.  None when this process already IS a rank (RANK / WORLD_SIZE set by torch.distributed.run) or N == 1.  A
@@ -325,7 +354,14 @@ def main():
     ap.add_argument("--no-extra", action="store_true")
     ap.add_argument("--no-roofline", action="store_true",
                     help="skip the roofline leg (profiling runs: the kernel trace then holds graph replays only, tools/pass_breakdown.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rgb, latents, pool8: what "
+                         "LcmHipPipeline.generate returns) as DIR/<name>.npy in float32, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
 
     # N > 1 without a torchrun environment: become the launcher.  The parent never touches the GPU (no torch import, no
     # library call before this point); every rank is a fresh child process.
@@ -507,6 +543,14 @@ def main():
 
     P = prime(B)
     dt, p50 = timed(P, args.steps, args.warmup)
+    dumped = None
+    if args.dump_outputs:
+        # the plan's outputs as left by the last timed replay, before any other leg launches a graph again
+        with torch.cuda.stream(P.lane.stream):
+            outs = {"rgb": P.rgb.cpu().numpy(), "latents": P.lat[P.UB - B:].cpu().numpy(), "pool8": P.pool8.cpu().numpy()}
+        dumped = {"dir": os.path.abspath(args.dump_outputs),
+                  "arrays": dump_outputs(args.dump_outputs, outs, DUMP_BUDGET_BYTES // world,
+                                         suffix=f"_rank{rank}" if world > 1 else "")}
     per_rank = [round(B * args.steps / dt, 3)]
     if dist is not None:
         with comm_stream(dev if backend == "nccl" else "cpu"):
@@ -528,6 +572,8 @@ def main():
                    "batch_per_gpu": B, "global_batch": world * B, "image": f"{S}x{S}", "lcm_steps": n,
                    "parallelism": f"independent requests x{world} (RCCL broadcast of prompt embeddings only)"},
     }
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
     if dist is not None:
         line["exchange"] = {"what": f"broadcast of [{world * B},77,{D}] fp16 prompt embeddings (rank 0's ClipTextHip output) before the "
                                     f"timed region; all_gather / all_reduce(MAX) of the per-rank times",

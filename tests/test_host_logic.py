@@ -744,6 +744,36 @@ def test_bench_traffic_lookup_reads_committed_pmc_table(tmp_path, capsys):
     assert st["mfma_busy_frac"] is None and "stale" in st["pmc_source"]
 
 
+def test_bench_dump_outputs_fits_the_budget_and_repeats(tmp_path):
+    """bench.py --dump-outputs: every array as float32 <name>.npy, whole when it fits its share of the budget, otherwise a
+    fixed sample (same positions every run); all files together within the budget."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    arrs = {"rgb": rng.integers(0, 256, (2, 256, 256, 3), dtype=np.uint8),
+            "latents": rng.standard_normal((2, 4, 32, 32)).astype(np.float32),
+            "pool8": rng.standard_normal((2, 4, 8, 8)).astype(np.float16)}
+    whole = bench.dump_outputs(str(tmp_path), arrs, 64 << 20)
+    assert all(v["sampled"] is None for v in whole.values())
+    for k, a in arrs.items():
+        got = np.load(tmp_path / f"{k}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32))
+    budget = 256 << 10
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"small{i}"
+        d.mkdir()
+        info = bench.dump_outputs(str(d), arrs, budget)
+        assert info["rgb"]["sampled"] and info["pool8"]["sampled"] is None
+        assert sum(f.stat().st_size for f in d.iterdir()) <= budget
+        runs.append({k: np.load(d / f"{k}.npy") for k in arrs})
+    assert all(np.array_equal(runs[0][k], runs[1][k]) for k in arrs)
+    assert np.isin(runs[0]["rgb"], arrs["rgb"].astype(np.float32)).all()
+
+
 def test_committed_counter_evidence_was_taken_on_the_kernels_in_the_tree():
     """PMC evidence went stale when a kernel changed after its counters were collected.  Every entry of this round's
     profiles/r04_pmc_summary.json and the traffic table record the sha256 of the kernel sources they were taken on
