@@ -190,6 +190,76 @@ def test_config4_sdxl_1024_parity(sdxl, guidance, steps):
     assert np.array_equal(rep["rgb"], out["rgb"]) and np.array_equal(rep["latents"], out["latents"])
 
 
+# ---- launch audit: every contraction / attention launch of the tuned passes against fp64 (tests/launch_audit.py) ------------
+# The passes tools/make_plans.py tunes, run eagerly (generate(want_float=True) -> pipe._enqueue on the lane stream) with the
+# shipped plan table -- never pipe.tune() -- and inputs filled the way generate() fills them.  The first launch of each distinct
+# shape is checked in full, every image of the batch.
+SD15_TUNED_PASSES = [(1, 512), (1, 768), (1, 256), (1, 128), (1, 192), (1, 64), (2, 512), (4, 512), (8, 512), (2, 256), (3, 128),
+                     (8, 768)]
+TUNED_STEPS = 4
+_AUDITED = {}                   # pass name -> (Audit.checks, plan keys the pass launched), for the coverage report
+
+
+def _audit_pass(hip, name, B, size, guidance=1.0, **kw):
+    from launch_audit import Audit
+    plans = hip.lanes[0].plans
+    before = set(plans)
+    with Audit() as au:
+        hip.generate(kw.pop("pe"), [300 + i for i in range(B)], size, size, TUNED_STEPS, guidance, want_float=True, **kw)
+    for k in set(plans) - before:          # the eager pass's plan is not kept (no graph was captured for it)
+        plans.pop(k)
+    torch.cuda.empty_cache()
+    launched = au.record_keys()
+    _AUDITED[name] = (au.checks, launched)
+    assert au.checked_keys() == launched, f"{name}: hook saw {len(au.checked_keys())} of {len(launched)} plan keys"
+    bad = [c for c in au.checks if not (c["ratio"] <= 1.0) or (c["stats_ratio"] is not None and not (c["stats_ratio"] <= 1.0))]
+    print(f"[audit] {name}: {len(au.checks)} launches checked, {len(launched)} plan keys "
+          f"({sum(k in au.table for k in launched)} in the table), worst ratio {max(c['ratio'] for c in au.checks):.3f}, "
+          f"worst statistics ratio {max((c['stats_ratio'] or 0.0) for c in au.checks):.3f}")
+    for c in bad:
+        print(f"[audit] {name} FAIL {c}")
+    assert not bad, f"{name}: {len(bad)} launches outside their fp64 error bound"
+    return au
+
+
+def _audit_report(table):
+    from launch_audit import config_table
+    checks = [c for name in _AUDITED for c in _AUDITED[name][0]]
+    reached = set().union(*(v[1] for v in _AUDITED.values()))
+    rows = config_table(checks)
+    table_cfgs = {(k[0],) + tuple(int(x) for x in v[:4]) for k, v in table.items()}
+    reached_cfgs = {(k[0],) + tuple(int(x) for x in table[k][:4]) for k in reached if k in table}
+    print(f"[audit] passes: {', '.join(_AUDITED)}")
+    print(f"[audit] {'kind':>4} {'bm':>4} {'bn':>4} {'splits':>6} {'variant':>7} {'checked':>7} {'worst':>7} {'stats':>7}")
+    for cfg in sorted(rows):
+        n, r, sr = rows[cfg]
+        print(f"[audit] {cfg[0]:>4} {cfg[1]:>4} {cfg[2]:>4} {cfg[3]:>6} {cfg[4]:>7} {n:>7} {r:>7.3f} {sr:>7.3f}")
+    print(f"[audit] table configurations reached: {len(reached_cfgs)} of {len(table_cfgs)}; "
+          f"table entries reached: {len(reached & set(table))} of {len(table)}")
+    for k in sorted(set(table) - reached):
+        print(f"[audit] unreached table entry {','.join(map(str, k))}: {list(table[k][:4])}")
+
+
+def test_audit_sd15_tuned_passes_fp64(sd15):
+    """The 12 SD1.5 passes tools/make_plans.py tunes: every launch shape within its fp64 bound, every plan key checked."""
+    hip = sd15["hip"]
+    for B, size in SD15_TUNED_PASSES:
+        _audit_pass(hip, f"sd15 B{B} {size}px", B, size, pe=_embeds(B, seed=60 + B))
+
+
+def test_audit_sdxl_1024_passes_fp64(sdxl):
+    """SDXL 1024x1024 without and with classifier-free guidance (the two SDXL passes of tools/make_plans.py)."""
+    hip = sdxl["hip"]
+    pe, pooled, tids = _sdxl_inputs()
+    _audit_pass(hip, "sdxl B1 1024px", 1, 1024, pe=pe, added=(pooled, tids))
+    g = torch.Generator().manual_seed(9)
+    neg, neg_pooled = torch.randn(1, 77, 2048, generator=g).half(), torch.randn(1, 1280, generator=g).half()
+    _audit_pass(hip, "sdxl B1 1024px cfg", 1, 1024, 5.0, pe=pe, added=(pooled, tids), negative_embeds=neg,
+                negative_added=(neg_pooled, tids))
+    from sdlcm_amd import lib
+    _audit_report(lib.known_plans())
+
+
 # ---- self-comparison checks (kept last) ----------------------------------------------------------------------------
 def test_config4_sdxl_1024_30step_is_deterministic(sdxl):
     """The full configs[4] run (30 steps) on the GPU only: two graph replays of the same request give identical bytes (graph

@@ -1335,3 +1335,37 @@ def test_staged_epilogue_of_plain_gemms_is_bit_identical(M, N, K, plan):
     if outs[0][1] is not None:
         assert torch.equal(outs[0][1], outs[1][1])
     close(outs[1][0], F.linear(a.float().cpu(), w.float().cpu(), b.float().cpu()) + r.float().cpu(), what="gemm + residual (staged)")
+
+
+# ---- entry points no sampler pass reaches, against fp64 ------------------------------------------------------------------
+def test_embed_tokens_clamps_ids_fp64():
+    """CLIP token + position embedding: ids 0 and vocab - 1, and out-of-range ids (negative, vocab, far above), which the
+    kernel clamps to [0, vocab - 1]."""
+    import launch_audit as la
+    vocab, S, D, B = 1000, 77, 768, 2
+    g = torch.Generator().manual_seed(11)
+    tok, pos = rnd(vocab, D, seed=12), rnd(S, D, seed=13)
+    ids = torch.randint(0, vocab, (B * S,), generator=g, dtype=torch.int32)
+    ids[:6] = torch.tensor([0, vocab - 1, -1, vocab, vocab + 12345, -(1 << 31)], dtype=torch.int32)
+    ids[-1] = vocab - 1
+    out = torch.full((B * S, D), float("nan"), dtype=torch.float16, device=DEV)
+    ops.embed_tokens(ids.to(DEV), tok.to(DEV), pos.to(DEV), out, B, S, D)
+    ref = tok.double()[ids.long().clamp(0, vocab - 1)] + pos.double().repeat(B, 1)
+    assert la.worst_ratio(out.cpu(), ref, la.store_bound(ref, la.U * ref.abs())) <= 1.0
+
+
+@pytest.mark.parametrize("in_place", [False, True])
+def test_axpy_past_grid_stride_span_fp64(in_place):
+    """LoRA merge out = base + alpha * delta over n above the 4096 x 256 x 8 elements one grid-stride sweep covers, alpha < 0,
+    and ``out`` = the live weight tensor itself."""
+    import launch_audit as la
+    n = 4096 * 256 * 8 + 8 * 1237
+    base, delta = rnd(n, seed=21), rnd(n, seed=22, scale=0.3)
+    alpha = -0.7431
+    b, d = base.to(DEV), delta.to(DEV)
+    out = b if in_place else torch.full_like(b, float("nan"))
+    ops.axpy(b, d, alpha, out)
+    a32 = float(np.float32(alpha))
+    ref = base.double().to(DEV) + a32 * delta.double().to(DEV)
+    E = 2 * la.U * (base.double().abs().to(DEV) + abs(a32) * delta.double().abs().to(DEV))
+    assert la.worst_ratio(out, ref, la.store_bound(ref, E)) <= 1.0
