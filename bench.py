@@ -3,6 +3,9 @@
 
   python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank per GPU)
   python bench.py ... --dump-outputs DIR               (also write the last timed step's outputs as DIR/<name>.npy)
+  python bench.py ... --full                           (also the roofline, CPU baseline and the other configs, see --help)
+
+A plain run does only what the headline figure needs: set up, warm up, time the steps, dump, print the line.
 
 A "step" is one pass of the hot path over one batch: a full 4-step LCM sample (4 x UNet + scheduler steps +
 VAE decode to RGB8) replayed from the captured hipGraph, inputs (prompt embeddings, per-request noise)
@@ -350,10 +353,15 @@ def main():
     ap.add_argument("--lcm-steps", type=int, default=None, help="sampler steps (default 4; 30 for --model sdxl)")
     ap.add_argument("--model", choices=("sd15", "sdxl"), default="sd15",
                     help="sd15 = BASELINE configs[1..3]; sdxl = configs[4] (SDXL-base 1024x1024, 30 steps, guidance 1.0, no CFG)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure and check everything else: at one GPU the roofline leg, "
+                         "batch 8, two lanes, 768x768, the worker loop, the CPU oracle baseline and SDXL; at N > 1 GPUs "
+                         "the batch-8 pass and a sharded generation check.  Off: the line carries the headline figure only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the other batch sizes, lanes, sizes and models")
     ap.add_argument("--no-roofline", action="store_true",
-                    help="skip the roofline leg (profiling runs: the kernel trace then holds graph replays only, tools/pass_breakdown.py)")
+                    help="with --full: skip the roofline leg and everything after it at one GPU (profiling runs: the kernel "
+                         "trace then holds graph replays only, tools/pass_breakdown.py)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (rgb, latents, pool8: what "
                          "LcmHipPipeline.generate returns) as DIR/<name>.npy in float32, at most 64 MB in all")
@@ -579,22 +587,23 @@ def main():
                                     f"timed region; all_gather / all_reduce(MAX) of the per-rank times",
                             "backend": "rccl" if backend == "nccl" else backend, "ms": round(bcast_ms.get(B, 0.0), 3),
                             "world_size": world}
-        # one real sharded generation through the same exchange code (distributed.run_sharded): every rank generates its shard
-        # of 2 * world requests with pipe.generate, RGB8 gathered on rank 0 (outside the timed region; a functional check)
-        from sdlcm_amd.distributed import run_sharded
-        cdev = torch.device(dev if backend == "nccl" else "cpu")
-        nreq = 2 * world
-        pe_all = prompt_embeddings(pipe, nreq) if rank == 0 else None
-        if pe_all is not None and backend != "nccl":
-            pe_all = pe_all.cpu()
+        if args.full:
+            # one real sharded generation through the same exchange code (distributed.run_sharded): every rank generates its shard
+            # of 2 * world requests with pipe.generate, RGB8 gathered on rank 0 (outside the timed region; a functional check)
+            from sdlcm_amd.distributed import run_sharded
+            cdev = torch.device(dev if backend == "nccl" else "cpu")
+            nreq = 2 * world
+            pe_all = prompt_embeddings(pipe, nreq) if rank == 0 else None
+            if pe_all is not None and backend != "nccl":
+                pe_all = pe_all.cpu()
 
-        def _gen(pe, seeds):
-            out = pipe.generate(pe, seeds, 64, 64, 2, 1.0)
-            return torch.from_numpy(out["rgb"]).to(cdev)
-        full = run_sharded(_gen, pe_all, [5000 + i for i in range(nreq)], cdev, gather_to=0)
-        if rank == 0:
-            line["exchange"]["sharded_check"] = {"requests": nreq, "gathered": list(full.shape), "ok": bool(full.shape[0] == nreq and full.any())}
-    if world > 1 and not args.no_extra and B == 1 and args.model == "sd15":
+            def _gen(pe, seeds):
+                out = pipe.generate(pe, seeds, 64, 64, 2, 1.0)
+                return torch.from_numpy(out["rgb"]).to(cdev)
+            gathered = run_sharded(_gen, pe_all, [5000 + i for i in range(nreq)], cdev, gather_to=0)
+            if rank == 0:
+                line["exchange"]["sharded_check"] = {"requests": nreq, "gathered": list(gathered.shape), "ok": bool(gathered.shape[0] == nreq and gathered.any())}
+    if world > 1 and args.full and not args.no_extra and B == 1 and args.model == "sd15":
         # BASELINE configs[2] itself: 8 requests per GPU in one batched pass on EVERY rank (64 requests on 8 GPUs); `value`
         # stays the batch-1-per-GPU workload so that the N = 1 line is comparable
         P8 = prime(8)
@@ -612,13 +621,14 @@ def main():
                                 "global_batch": world * 8, "exchange_ms": round(bcast_ms.get(8, 0.0), 3),
                                 "workload": f"BASELINE configs[2]: {world * 8} requests, 8 per GPU in one batched pass on each of {world} GPUs "
                                             f"(aggregate over ranks, max-over-ranks time)"}
-    if rank == 0 and world == 1 and not args.no_roofline:
-        line["roofline"] = roofline_leg(pipe, P, 1.0, dt / args.steps * 1e3)
+    if rank == 0 and world == 1:
         if args.model == "sdxl":
             fl_img = (6.761e12 * n + 10.470e12) * (S * S) / (1024 * 1024)
         else:
             fl_img = 5.74e12 * (S * S) / (512 * 512) * n / 4
         line["pipeline_tflops"] = round(fl_img * B / (dt / args.steps) / 1e12, 1)
+    if rank == 0 and world == 1 and args.full and not args.no_roofline:
+        line["roofline"] = roofline_leg(pipe, P, 1.0, dt / args.steps * 1e3)
         if not args.no_extra and B == 1 and args.model == "sd15":
             P8 = prime(8)
             dt8, p508 = timed(P8, max(3, args.steps // 4), 1)

@@ -1,5 +1,5 @@
 #!/bin/bash
-# One box session: bench JSON (default flags), then rocprofv3 kernel traces of batch 1 and batch 8 graph replays ->
+# One box session: bench JSON (--full), then rocprofv3 kernel traces of batch 1 and batch 8 graph replays ->
 # per-kernel stats, pass breakdown and launch-by-launch sequence under gpurun_out/$1 (default "prof").
 set -o pipefail
 OUT=gpurun_out/${1:-prof}
@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 export LCM_TUNE_CACHE=/tmp/tc.json
 mkdir -p $OUT
 if [ -z "$SKIP_BENCH" ]; then
-timeout -k 10 500 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 500 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 echo "bench done" && cut -c1-300 $OUT/bench.json
 fi
 for t in b1 b8; do
