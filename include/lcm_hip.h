@@ -337,6 +337,32 @@ int lcm_vae_place_tile(const void* tile, int th, int tw, void* out_u8, void* out
  * re-merged in place, so captured graphs stay valid). */
 int lcm_axpy_f16(const void* base, const void* delta, float alpha, void* out, int64_t n, void* stream);
 
+/* ---- super-resolution post-process (server/lcm_sr_server.py SuperResWorker, upscale_once): the ONNX model zoo's
+ * super-resolution-10 (conv1 5x5 1->64, conv2 3x3 64->64, conv3 3x3 64->32, each + ReLU; conv4 3x3 32->r*r; pixel shuffle r;
+ * r = 3 is the only factor the kernels implement) on the luma plane, plus PIL's bicubic xr of Cb / Cr and the merge.
+ * Images are RGB8 [H][W][3], planes uint8 row major.  A pass cuts the W x H image into tile_w x tile_h tiles: x starts
+ * min(i * tile_w, W - tile_w) for i < ceil(W / tile_w), y likewise, numbered row-major (y outer).  Each tile is an independent
+ * network input, zero padded at ITS OWN border.  Tile activations are fp16 NHWC [T][tile_h][tile_w][C] for the T tiles
+ * [t0, t0 + T) of the plan (any split of the plan into such chunks gives the same bits).  Weights are fp16: conv1 [25 taps][64],
+ * conv2 / conv3 [Cout][ky][kx][Cin = 64], conv4 [ky][kx][Cin = 32][r*r]; biases fp32.
+ *   conv1:          RGB8 -> Y = PIL's integer luma, fp16(Y / 255), conv1 + bias + ReLU -> [T][th][tw][64]
+ *   conv3x3:        cout 64 (conv2) or 32 (conv3), 3x3 pad 1 per tile + bias + ReLU; in [T][th][tw][64]; 16-byte aligned
+ *   conv4_shuffle:  y_out[r*gy + i][r*gx + j] = uint8(clip(255 * (conv4[i*r + j] + bias), 0, 255)) (truncation), written
+ *                   only for the input pixels (gx, gy) the tile OWNS -- the tile with the largest covering x start and y
+ *                   start, i.e. the one a row-major overwrite leaves on top -- so each of the rW x rH bytes is written
+ *                   once by exactly one tile; y_out [rH][rW]
+ *   chroma_h:       Cb / Cr of RGB8 (PIL's 6-bit tables, within 1 of PIL), PIL's 8-bit bicubic (a = -0.5) along x to rW
+ *                   columns -> cbcr_h [H][rW][2] (uint8 as PIL keeps its intermediate)
+ *   merge:          PIL's bicubic along y to rH rows of cbcr_h, merged with y_plane, YCbCr -> RGB8 (PIL's tables, within 1)
+ *                   -> rgb_out [rH][rW][3] */
+int lcm_sr_conv1(const void* rgb, int W, int H, int tile_w, int tile_h, int t0, int ntiles, const void* w1, const void* b1,
+                 void* out, void* stream);
+int lcm_sr_conv3x3(const void* in, int T, int th, int tw, int cout, const void* w, const void* bias, void* out, void* stream);
+int lcm_sr_conv4_shuffle(const void* in, int W, int H, int tile_w, int tile_h, int t0, int ntiles, const void* w4,
+                         const void* b4, int r, void* y_out, void* stream);
+int lcm_sr_chroma_h(const void* rgb, int W, int H, int r, void* cbcr_h, void* stream);
+int lcm_sr_merge(const void* y_plane, const void* cbcr_h, int W, int H, int r, void* rgb_out, void* stream);
+
 /* ---- hipGraph capture of the 4-step sampler loop + VAE ---- */
 int lcm_graph_begin(void* stream);
 int lcm_graph_end(void* stream, void** graph_exec_out);

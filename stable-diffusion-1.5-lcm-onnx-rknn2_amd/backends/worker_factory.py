@@ -90,3 +90,13 @@ def create_hip_worker(worker_id: int):
     if q is not None:
         w.bind_queue(q)
     return w
+
+
+def create_hip_sr_worker(worker_id: int, model_path: str = None, input_size: int = None, output_size: int = None):
+    """The HIP super-resolution worker with the server's SR_* settings as defaults (server/lcm_sr_server.py:512-518)."""
+    from .sr_worker import HipSuperResWorker
+    if model_path is None:
+        model_path = os.environ.get("SR_MODEL_PATH") or os.path.join(os.environ.get("MODEL_ROOT", ""), "super-resolution-10.rknn")
+    return HipSuperResWorker(worker_id, model_path,
+                             int(input_size if input_size is not None else os.environ.get("SR_INPUT_SIZE", "224")),
+                             int(output_size if output_size is not None else os.environ.get("SR_OUTPUT_SIZE", "672")))

@@ -90,6 +90,11 @@ _SIGS = {
                            C.POINTER(_i), _vp],
     "lcm_groupnorm_affine_f16": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp],
     "lcm_device_info": [_i, C.c_char_p, _i, C.POINTER(_i), C.POINTER(C.c_uint64)],
+    "lcm_sr_conv1": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "lcm_sr_conv3x3": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "lcm_sr_conv4_shuffle": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp],
+    "lcm_sr_chroma_h": [_vp, _i, _i, _i, _vp, _vp],
+    "lcm_sr_merge": [_vp, _vp, _i, _i, _i, _vp, _vp],
 }
 EXPORTS = tuple(sorted(list(_SIGS) + ["lcm_last_error", "lcm_version", "lcm_groupnorm_ws_bytes", "lcm_stats_bytes", "lcm_png_bound"]))
 
