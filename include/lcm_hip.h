@@ -301,6 +301,18 @@ int lcm_timestep_embedding_steps(const float* t_host, int nsteps, void* out, int
 int lcm_scheduler_step(const void* eps, const void* eps_uncond, float guidance, void* lat, const void* noise,
                        const float* coef6, int last, int B, int h, int w, void* stream);
 
+/* The same step for any prediction type of the model output m (after CFG, applied to m exactly as above):
+ *   LCM_PRED_EPSILON  x0 = (x - sqrt_beta_t m) / sqrt_alpha_t      (lcm_scheduler_step: identical kernel, identical bits)
+ *   LCM_PRED_V        x0 = sqrt_alpha_t x - sqrt_beta_t m          (v-prediction: SD 2.x-768 and most SD2 fine-tunes)
+ *   LCM_PRED_SAMPLE   x0 = m
+ * then den = c_out x0 + c_skip x, and x <- last ? den : sqrt_alpha_prev den + sqrt_beta_prev noise (diffusers'
+ * LCMScheduler.step).  Any other prediction_type returns LCM_EINVAL before anything is enqueued. */
+#define LCM_PRED_EPSILON 0
+#define LCM_PRED_V 1
+#define LCM_PRED_SAMPLE 2
+int lcm_scheduler_step_ex(const void* eps, const void* eps_uncond, float guidance, void* lat, const void* noise,
+                          const float* coef6, int last, int prediction_type, int B, int h, int w, void* stream);
+
 /* ---- adaptive_avg_pool2d(lat,(8,8)) -> fp16 [B,4,8,8] (run_job_with_latents, backends/cuda_worker.py:299-304) */
 int lcm_latents_pool8(const void* lat, void* out_f16, int B, int h, int w, void* stream);
 

@@ -5,9 +5,12 @@
 ``pipeline.LcmHipPipeline``.
 
 Env (as the reference, backends/cuda_worker.py:43-61):
-  MODEL_ROOT, MODEL   checkpoint location (diffusers directory).  MODEL=synthetic (or
-                      LCM_HIP_SYNTHETIC=1) selects seeded synthetic weights of the SD1.5 architecture --
+  MODEL_ROOT, MODEL   checkpoint location (diffusers directory or single .safetensors file).  MODEL=synthetic (or
+                      LCM_HIP_SYNTHETIC=1) selects seeded synthetic weights of the SD1.5 architecture, MODEL=synthetic-sd2
+                      those of SD 2.1-768 (865 M UNet, OpenCLIP-H text tower, v-prediction schedule) --
                       no checkpoint ships with the reference.
+  LCM_PREDICTION_TYPE        epsilon | v_prediction | sample: overrides the prediction type guessed for a single-file
+                             checkpoint (weights.single_file_prediction_type; e.g. epsilon for SD 2.x-base)
   CUDA_DEVICE / HIP_DEVICE   default cuda:0 (torch's name for the HIP device)
   CUDA_DTYPE                 fp16 (default).  bf16 / fp32 -- which the reference honours -- are REFUSED unless LCM_HIP_DTYPE=fp16
                              says to run them in this backend's one arithmetic (fp16 operands, fp32 accumulation)
@@ -335,7 +338,9 @@ class HipLcmWorker:
         device = pick_device(worker_id, torch.cuda.device_count())      # LCM_DEVICES=all: worker i -> GPU i mod N
         share = os.environ.get("LCM_SHARE_ENGINE", "1").lower() not in ("0", "false", "no", "off")
         from .styles import STYLE_REGISTRY
-        ekey = (self.FAMILY, device, "synthetic" if synthetic else os.path.join(model_root, model_name),
+        # synthetic weights: the engine is keyed by the synthetic model's name (synthetic / synthetic-sd2 differ)
+        synth_name = model_name if model_name.startswith("synthetic") else "synthetic"
+        ekey = (self.FAMILY, device, synth_name if synthetic else os.path.join(model_root, model_name),
                 tuple(sorted((sid, sd.path()) for sid, sd in STYLE_REGISTRY.items())))
         with _ENGINES_LOCK:
             ref = _ENGINES.get(ekey) if share else None
@@ -349,18 +354,32 @@ class HipLcmWorker:
             print(f"[hip] worker {worker_id} ({self.FAMILY}) attached to the resident engine on {device} ({eng.refs} workers)")
             return
         sched = LCMSchedule()
-        clip_sd = None
-        if synthetic:
+        clip_sd = text_cfg = None
+        if synthetic and synth_name == "synthetic-sd2" and self.FAMILY == "sd15":
+            from ..clip import CLIP_H
+            from ..config import SD2_UNET, unet_config
+            from ..scheduler import SD21_768_SCHEDULE
+            usd, ucfg, vsd, vcfg = _weights.synthetic_sd2_unet(), unet_config(SD2_UNET), _weights.synthetic_vae(), None
+            sched, text_cfg = LCMSchedule(**SD21_768_SCHEDULE), dict(CLIP_H)
+            ckpt_root, ckpt, format_name = None, synth_name, "synthetic"
+        elif synthetic:
             usd, ucfg, vsd, vcfg = self._synthetic_weights()
             ckpt_root, ckpt, format_name = None, "synthetic", "synthetic"
         else:
             ckpt = os.path.join(model_root, model_name)
             if os.path.isdir(ckpt) and os.path.exists(os.path.join(ckpt, "model_index.json")):
                 usd, ucfg, vsd, vcfg = _weights.load_diffusers_dir(ckpt)          # cuda_worker.py:66-77
+                sched = LCMSchedule.from_config_file(os.path.join(ckpt, "scheduler", "scheduler_config.json"))
                 format_name = "diffusers"
             elif os.path.isfile(ckpt) and ckpt.endswith(".safetensors"):
-                loader = _weights.load_single_file if self.FAMILY == "sd15" else _weights.load_single_file_sdxl
-                usd, ucfg, vsd, vcfg, clip_sd = loader(ckpt)                       # cuda_worker.py:78-85 / :330-352
+                # a file has no scheduler/ folder: the loader says what its UNet predicts (LCM_PREDICTION_TYPE overrides)
+                if self.FAMILY == "sd15":
+                    usd, ucfg, vsd, vcfg, clip_sd, meta = _weights.load_single_file(ckpt, with_meta=True)   # cuda_worker.py:78-85
+                    pred, text_cfg = meta["prediction_type"], meta["text_config"]
+                else:
+                    usd, ucfg, vsd, vcfg, clip_sd = _weights.load_single_file_sdxl(ckpt)                   # cuda_worker.py:330-352
+                    pred = _weights.single_file_prediction_type({}, False)
+                sched = LCMSchedule(prediction_type=pred)
                 format_name = "single-file"
             else:
                 raise RuntimeError(f"{ckpt}: expected a diffusers directory (model_index.json) or a .safetensors file"
@@ -369,7 +388,6 @@ class HipLcmWorker:
             if (cad in (2048, 1280)) != (self.FAMILY == "sdxl"):
                 raise RuntimeError(f"Loaded UNet with cross_attention_dim={cad} into the {self.FAMILY} worker "
                                    "(SD1.5: 768/1024, SDXL: 2048)")                  # cuda_worker.py:114-116
-            sched = LCMSchedule.from_config_file(os.path.join(ckpt, "scheduler", "scheduler_config.json"))
             ckpt_root = ckpt if format_name == "diffusers" else None
         if self.FAMILY == "sd15" and vcfg is not None:
             # only the SDXL pipeline honours the VAE's force_upcast (StableDiffusionXLPipeline.upcast_vae); SD1.5 decodes in
@@ -379,7 +397,7 @@ class HipLcmWorker:
         eng.device = device
         eng.pipe = LcmHipPipeline(usd, vsd, ucfg, vcfg, device=device, schedule=sched)
         with torch.cuda.stream(eng.pipe.stream):
-            self._load_text_encoders(eng, device, ckpt_root, clip_sd)
+            self._load_text_encoders(eng, device, ckpt_root, clip_sd, text_cfg)
         eng.refs = 1
         self._engine = eng
         self._load_styles(eng)
@@ -450,9 +468,10 @@ class HipLcmWorker:
         return _weights.synthetic_unet(), None, _weights.synthetic_vae(), None
 
     @staticmethod
-    def _load_text_encoders(eng, device, ckpt_root, clip_sd):
-        # CLIP text encoder on the same kernels (checkpoint text_encoder/ when present, else synthetic CLIP-L weights)
-        eng.encode = HipPromptEncoder(device, ckpt_root, clip_sd)
+    def _load_text_encoders(eng, device, ckpt_root, clip_sd, text_cfg=None):
+        # CLIP text encoder on the same kernels (checkpoint text_encoder/ when present, else synthetic weights: CLIP-L, or
+        # text_cfg's tower -- CLIP-H for synthetic-sd2)
+        eng.encode = HipPromptEncoder(device, ckpt_root, clip_sd, text_cfg)
         if eng.encode.enc.D != eng.pipe.unet.ctx_dim:
             raise RuntimeError(f"text encoder width {eng.encode.enc.D} != UNet cross_attention_dim {eng.pipe.unet.ctx_dim}")
 
@@ -737,7 +756,7 @@ class HipLcmSDXLWorker(HipLcmWorker):
                 _weights.synthetic_state_dict(_weights.vae_param_spec(vcfg), 1), vcfg)
 
     @staticmethod
-    def _load_text_encoders(eng, device, ckpt_root, clip_sd):
+    def _load_text_encoders(eng, device, ckpt_root, clip_sd, text_cfg=None):
         from ..clip import CLIP_BIGG, CLIP_L, ClipTextHip, HashTokenizer, load_clip_dir, synthetic_clip
         from ..prompt import make_tokenizer
         eng.enc, eng.tok = [], []

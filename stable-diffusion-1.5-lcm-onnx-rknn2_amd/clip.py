@@ -24,6 +24,11 @@ CLIP_GRAPH = os.environ.get("LCM_CLIP_GRAPH", "1") != "0"
 CLIP_BIGG = dict(vocab_size=49408, hidden_size=1280, intermediate_size=5120, num_hidden_layers=32, num_attention_heads=20,
                  max_position_embeddings=77, hidden_act="gelu", layer_norm_eps=1e-5, projection_dim=1280)
 
+# OpenCLIP ViT-H/14 text tower as SD 2.x conditions on it (diffusers' text_encoder of SD 2.0 / 2.1, CLIPTextModel): the
+# 24-layer tower cut after its penultimate block (23 layers), then ln_final; 1024 wide, 16 heads, exact GELU.
+CLIP_H = dict(vocab_size=49408, hidden_size=1024, intermediate_size=4096, num_hidden_layers=23, num_attention_heads=16,
+              max_position_embeddings=77, hidden_act="gelu", layer_norm_eps=1e-5)
+
 CLIP_L = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12,
               max_position_embeddings=77, hidden_act="quick_gelu", layer_norm_eps=1e-5)
 
@@ -60,6 +65,11 @@ def synthetic_clip(cfg=None, seed=2):
     for n in ("embeddings.token_embedding.weight", "embeddings.position_embedding.weight"):
         sd[n] = (sd[n].float() * (sd[n].shape[1] ** 0.5) * 0.5).to(torch.float16)
     return sd
+
+
+def synthetic_clip_h(seed=2):
+    """Seeded synthetic weights of the SD 2.x text encoder (CLIP_H)."""
+    return synthetic_clip(CLIP_H, seed)
 
 
 def load_clip_dir(d: str):

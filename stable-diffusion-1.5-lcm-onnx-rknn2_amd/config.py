@@ -24,6 +24,11 @@ SDXL_UNET = dict(
     addition_time_embed_dim=256, projection_class_embeddings_input_dim=2816,
 )
 
+# SD 2.x UNet (SD 2.0 / 2.1, base and 768): the SD1.5 layout with 64-wide heads (heads = C / 64 per level), OpenCLIP-H
+# context (1024 wide), linear proj_in / proj_out and no LCM guidance embedding.  The VAE is SD1.5's.
+SD2_UNET = dict(SD15_UNET, attention_head_dim=(5, 10, 20, 20), cross_attention_dim=1024, time_cond_proj_dim=None,
+                use_linear_projection=True)
+
 SD15_VAE = dict(
     latent_channels=4, out_channels=3, block_out_channels=(128, 256, 512, 512),
     layers_per_block=2, norm_num_groups=32, scaling_factor=0.18215, sample_size=512,

@@ -52,6 +52,7 @@ _SIGS = {
     "lcm_linear_rows_f16": [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "lcm_timestep_embedding_steps": [_vp, _i, _vp, _i, _i, _vp],
     "lcm_scheduler_step": [_vp, _vp, _f, _vp, _vp, C.POINTER(C.c_float), _i, _i, _i, _i, _vp],
+    "lcm_scheduler_step_ex": [_vp, _vp, _f, _vp, _vp, C.POINTER(C.c_float), _i, _i, _i, _i, _i, _vp],
     "lcm_latents_pool8": [_vp, _vp, _i, _i, _i, _vp],
     "lcm_png_encode_rgb8": [_vp, _i, _i, C.c_longlong, _i, _vp, C.c_longlong, C.POINTER(C.c_longlong)],
     "lcm_stream_create": [C.POINTER(_vp)],
@@ -169,3 +170,8 @@ def check(rc: int, what: str = ""):
     if rc != 0:
         msg = load().lcm_last_error().decode("utf-8", "replace")
         raise LcmHipError(f"{what or 'lcm call'} failed (rc={rc}): {msg}")
+
+
+# prediction types of lcm_scheduler_step_ex (include/lcm_hip.h)
+LCM_PRED_EPSILON, LCM_PRED_V, LCM_PRED_SAMPLE = 0, 1, 2
+PREDICTION_TYPES = {"epsilon": LCM_PRED_EPSILON, "v_prediction": LCM_PRED_V, "sample": LCM_PRED_SAMPLE}

@@ -427,12 +427,21 @@ def timestep_embedding(t, out, B, dim):
     return out
 
 
-def scheduler_step(eps, lat, noise, coef6, last, B, h, w, *, eps_uncond=None, guidance=1.0):
+def scheduler_step(eps, lat, noise, coef6, last, B, h, w, *, eps_uncond=None, guidance=1.0, pred="epsilon"):
+    """One LCMScheduler.step in place on ``lat``.  pred: the model output's prediction type ("epsilon" | "v_prediction" |
+    "sample"); epsilon goes through lcm_scheduler_step as it always has."""
     L = _lib.load()
     arr = (C.c_float * 6)(*[float(c) for c in coef6])
-    rc = L.lcm_scheduler_step(_p(eps), _p(eps_uncond), float(guidance), _p(lat), _p(noise), arr, int(bool(last)),
-                              B, h, w, _stream())
-    _lib.check(rc, "lcm_scheduler_step")
+    if pred == "epsilon":
+        rc = L.lcm_scheduler_step(_p(eps), _p(eps_uncond), float(guidance), _p(lat), _p(noise), arr, int(bool(last)),
+                                  B, h, w, _stream())
+        _lib.check(rc, "lcm_scheduler_step")
+        return lat
+    if pred not in _lib.PREDICTION_TYPES:
+        raise ValueError(f"unknown prediction type {pred!r}: expected one of {sorted(_lib.PREDICTION_TYPES)}")
+    rc = L.lcm_scheduler_step_ex(_p(eps), _p(eps_uncond), float(guidance), _p(lat), _p(noise), arr, int(bool(last)),
+                                 _lib.PREDICTION_TYPES[pred], B, h, w, _stream())
+    _lib.check(rc, "lcm_scheduler_step_ex")
     return lat
 
 

@@ -203,11 +203,13 @@ class LcmHipPipeline:
                          ta=ta_all[i * UB:(i + 1) * UB] if ta_all is not None else None)
             coef, last = self.sched.step_coefficients(ts, i)
             noise = P.noise[min(i, P.noise.shape[0] - 1)]
+            pred = self.sched.prediction_type
             if P.do_cfg:   # rows [0,B) = negative prompt, [B,2B) = prompt
-                ops.scheduler_step(P.eps[B:], P.lat[B:], noise, coef, last, B, h, w, eps_uncond=P.eps[:B], guidance=guidance)
+                ops.scheduler_step(P.eps[B:], P.lat[B:], noise, coef, last, B, h, w, eps_uncond=P.eps[:B], guidance=guidance,
+                                   pred=pred)
                 P.lat[:B].copy_(P.lat[B:])
             else:
-                ops.scheduler_step(P.eps, P.lat, noise, coef, last, B, h, w)
+                ops.scheduler_step(P.eps, P.lat, noise, coef, last, B, h, w, pred=pred)
         final = P.lat[B:] if P.do_cfg else P.lat
         ops.latents_pool8(final, P.pool8, B, h, w)
         if want_float and P.img_f32 is None:

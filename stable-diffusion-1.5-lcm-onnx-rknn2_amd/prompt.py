@@ -54,7 +54,9 @@ def make_tokenizer(ckpt_root, sub, vocab_size, real_weights):
 class HipPromptEncoder:
     """prompts (list[str]) -> fp16 [B, 77, D] on the device, computed by the native CLIP text encoder."""
 
-    def __init__(self, device, ckpt_root: str | None = None, clip_sd: dict | None = None):
+    def __init__(self, device, ckpt_root: str | None = None, clip_sd: dict | None = None, clip_cfg: dict | None = None):
+        """clip_cfg: settings of a single-file text tower that its tensors do not show (SD 2.x: hidden_act="gelu",
+        from weights.load_single_file's meta); the shapes give the rest."""
         te = os.path.join(ckpt_root, "text_encoder") if ckpt_root else None
         if clip_sd is not None:                      # text encoder carried inside a single-file checkpoint
             sd = clip_sd
@@ -63,12 +65,13 @@ class HipPromptEncoder:
                        vocab_size=sd["embeddings.token_embedding.weight"].shape[0],
                        intermediate_size=sd["encoder.layers.0.mlp.fc1.weight"].shape[0],
                        num_attention_heads=sd["embeddings.token_embedding.weight"].shape[1] // 64)
+            cfg.update(clip_cfg or {})
             self.source = "single-file"
         elif te and os.path.isdir(te):
             sd, cfg = load_clip_dir(te)
             self.source = "checkpoint"
         else:
-            sd, cfg = synthetic_clip(), None
+            sd, cfg = synthetic_clip(clip_cfg), clip_cfg
             self.source = "synthetic"
         self.enc = ClipTextHip(sd, cfg, device=device)
         self.tokenize = make_tokenizer(ckpt_root, "tokenizer", self.enc.cfg["vocab_size"], self.source != "synthetic")

@@ -11,11 +11,23 @@ import os
 import numpy as np
 
 
+PREDICTION_TYPES = ("epsilon", "v_prediction", "sample")
+
+# scheduler_config.json of SD 2.1-768 (v-prediction; set_alpha_to_one never matters to LCM: its last step uses its own t)
+SD21_768_SCHEDULE = dict(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
+                         set_alpha_to_one=False, prediction_type="v_prediction")
+
+
 class LCMSchedule:
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
-                 original_inference_steps=50, timestep_scaling=10.0, sigma_data=0.5, set_alpha_to_one=True, **_ignored):
+                 original_inference_steps=50, timestep_scaling=10.0, sigma_data=0.5, set_alpha_to_one=True,
+                 prediction_type="epsilon", **_ignored):
         if beta_schedule != "scaled_linear":
             raise ValueError(f"unsupported beta_schedule {beta_schedule!r}")
+        # what the UNet predicts (LCMScheduler.step): epsilon (SD1.5, SD 2.x-base), v_prediction (SD 2.x-768), sample
+        if prediction_type not in PREDICTION_TYPES:
+            raise ValueError(f"unsupported prediction_type {prediction_type!r}: expected one of {', '.join(PREDICTION_TYPES)}")
+        self.prediction_type = prediction_type
         self.num_train_timesteps = int(num_train_timesteps)
         betas = np.linspace(beta_start ** 0.5, beta_end ** 0.5, self.num_train_timesteps, dtype=np.float32) ** 2
         self.alphas_cumprod = np.cumprod((1.0 - betas).astype(np.float32), dtype=np.float32)
@@ -32,7 +44,7 @@ class LCMSchedule:
         with open(path) as f:
             cfg = json.load(f)
         keys = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "original_inference_steps",
-                "timestep_scaling", "sigma_data", "set_alpha_to_one")
+                "timestep_scaling", "sigma_data", "set_alpha_to_one", "prediction_type")
         return cls(**{k: cfg[k] for k in keys if k in cfg})
 
     def timesteps(self, n: int) -> np.ndarray:

@@ -192,6 +192,12 @@ def synthetic_unet(cfg=None, seed=0):
     return synthetic_state_dict(unet_param_spec(cfg), seed)
 
 
+def synthetic_sd2_unet(seed=0):
+    """Seeded synthetic weights of the SD 2.x UNet (config.SD2_UNET, 865 M parameters)."""
+    from .config import SD2_UNET
+    return synthetic_unet(SD2_UNET, seed)
+
+
 def synthetic_vae(cfg=None, seed=1):
     return synthetic_state_dict(vae_param_spec(cfg), seed)
 
@@ -221,6 +227,10 @@ def load_diffusers_dir(root: str):
 
     ju, ucfg = cfg_of("unet", unet_config())
     ucfg["time_cond_proj_dim"] = ju.get("time_cond_proj_dim")
+    # upcast_attention (SD 2.1) asks for QK^T and softmax in fp32.  The attention kernel already does that: QK^T accumulates
+    # in fp32 from fp16 operands and the softmax runs in fp32; the 64-wide heads' d^-0.5 prescale is an exact 2^-3.  So the
+    # key is accepted and changes nothing.
+    ucfg["upcast_attention"] = bool(ju.get("upcast_attention") or False)
     if "down_block_types" in ju:
         ucfg["down_attn"] = tuple("CrossAttn" in t for t in ju["down_block_types"])
     _, vcfg = cfg_of("vae", vae_config())
@@ -324,12 +334,42 @@ def _ldm_vae_key(k: str, n_up: int = 4):
     return None
 
 
-def load_single_file(path: str):
+def single_file_prediction_type(raw: dict, sd2: bool) -> str:
+    """What the UNet of a single-file checkpoint predicts.  The file does not say: LCM_PREDICTION_TYPE overrides the guess
+    (e.g. ``epsilon`` for SD 2.x-base).  SD1.5 files: epsilon.  SD 2.x files: v_prediction, unless the file carries a
+    global_step of 875000 (the SD 2.x-base release), which is the rule diffusers' from_single_file applies to v2 files.
+    [EXT] That rule is restated from diffusers' published conversion code; diffusers itself was not available to check it."""
+    env = (os.environ.get("LCM_PREDICTION_TYPE") or "").strip()
+    if env:
+        from .scheduler import PREDICTION_TYPES
+        if env not in PREDICTION_TYPES:
+            raise ValueError(f"LCM_PREDICTION_TYPE={env!r}: expected one of {', '.join(PREDICTION_TYPES)}")
+        return env
+    if not sd2:
+        return "epsilon"
+    gs = raw.get("global_step")
+    return "epsilon" if gs is not None and int(gs.reshape(-1)[0]) == 875000 else "v_prediction"
+
+
+def load_single_file(path: str, with_meta: bool = False):
     """Original-layout .safetensors checkpoint -> (unet_sd, unet_cfg, vae_sd, vae_cfg, clip_sd | None).
-    Architecture numbers are inferred from tensor shapes, then audited against the graph like the directory loader."""
+    Architecture numbers are inferred from tensor shapes, then audited against the graph like the directory loader.
+
+    SD1.5: CLIP-L text tower under cond_stage_model.transformer.* (transformers names).  SD 2.x: OpenCLIP-H text tower under
+    cond_stage_model.model.*; the UNet gets 64-wide heads per level and linear projections, and the text dict keeps
+    resblocks 0 .. n-2 with ln_final as its final LayerNorm (SD 2.x conditions on the penultimate block, normalised: what
+    diffusers' conversion keeps, 23 of 24 layers).
+    with_meta=True appends dict(family="sd15" | "sd2", prediction_type, text_config): the scheduler's prediction type
+    (single_file_prediction_type) and the text-encoder settings that the tensors do not show (hidden_act)."""
     from safetensors.torch import load_file
     raw = load_file(path)
     usd, vsd, csd = {}, {}, {}
+    oc = "cond_stage_model.model."
+    sd2 = any(k.startswith(oc) for k in raw)
+    if sd2:
+        n_res = 1 + max((int(k.split(".")[4]) for k in raw if k.startswith(oc + "transformer.resblocks.")), default=-1)
+        if n_res < 2:
+            raise RuntimeError(f"{path}: OpenCLIP text tower with {n_res} resblocks (SD 2.x needs its penultimate one)")
     for k, v in raw.items():
         if k.startswith("model.diffusion_model."):
             kk = k[len("model.diffusion_model."):]
@@ -345,6 +385,14 @@ def load_single_file(path: str):
             kk = kk[len("text_model."):] if kk.startswith("text_model.") else kk
             if "position_ids" not in kk:
                 csd[kk] = v.to(torch.float16)
+        elif k.startswith(oc):
+            kk = k[len(oc):]
+            if kk.startswith("transformer.resblocks.") and int(kk.split(".")[2]) >= n_res - 1:
+                continue                                                      # the last block: SD 2.x never uses it
+            if kk == "text_projection":
+                continue                                                      # CLIPTextModel has no projection
+            for nk, tf in _openclip_text_key(kk):
+                csd[nk] = (v if tf is None else v.chunk(3, dim=0)[tf[1]]).to(torch.float16).contiguous()
     if "conv_in.weight" not in usd:
         raise RuntimeError(f"{path}: no model.diffusion_model.* tensors (not an original-layout SD checkpoint)")
     boc = (usd["conv_in.weight"].shape[0], usd["down_blocks.1.resnets.0.conv1.weight"].shape[0],
@@ -353,6 +401,8 @@ def load_single_file(path: str):
                             cross_attention_dim=usd["down_blocks.0.attentions.0.transformer_blocks.0.attn2.to_k.weight"].shape[1],
                             time_cond_proj_dim=(usd["time_embedding.cond_proj.weight"].shape[1]
                                                 if "time_embedding.cond_proj.weight" in usd else None)))
+    if sd2:
+        ucfg.update(attention_head_dim=tuple(c // 64 for c in boc), use_linear_projection=True)
     vboc = (vsd["decoder.up_blocks.3.resnets.0.conv1.weight"].shape[0], vsd["decoder.up_blocks.2.resnets.0.conv1.weight"].shape[0],
             vsd["decoder.up_blocks.1.resnets.0.conv1.weight"].shape[0], vsd["decoder.conv_in.weight"].shape[0])
     vcfg = vae_config(dict(block_out_channels=vboc))
@@ -366,11 +416,16 @@ def load_single_file(path: str):
             raise RuntimeError(f"checkpoint/graph mismatch at vae '{name}': missing")
         if tuple(vsd[name].shape) != tuple(shape):
             vsd[name] = vsd[name].reshape(shape)
-    return usd, ucfg, vsd, vcfg, (csd or None)
+    if not with_meta:
+        return usd, ucfg, vsd, vcfg, (csd or None)
+    meta = dict(family="sd2" if sd2 else "sd15", prediction_type=single_file_prediction_type(raw, sd2),
+                text_config=dict(hidden_act="gelu") if sd2 else {})
+    return usd, ucfg, vsd, vcfg, (csd or None), meta
 
 
 def _openclip_text_key(k: str):
-    """'conditioner.embedders.1.model.' key (prefix stripped; OpenCLIP text tower as SDXL single files carry it) ->
+    """'conditioner.embedders.1.model.' / 'cond_stage_model.model.' key (prefix stripped; OpenCLIP text tower as SDXL / SD 2.x
+    single files carry it) ->
     list of (transformers CLIPTextModelWithProjection key without 'text_model.', transform) pairs."""
     if k == "token_embedding.weight":
         return [("embeddings.token_embedding.weight", None)]
