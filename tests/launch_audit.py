@@ -23,12 +23,52 @@ FeedForward) that operand carries H * |a| + SUB more, which enters E as sum_k (H
 absolute values.  Every sum of absolute values is a second fp64 GEMM on |a| and |w|.
 
 The references use torch float64 matmuls (rocBLAS on the GPU, or the CPU) -- never the project's kernels.
+
+The other entry points of a pass (``CHECKED``: norms, softmax, gathers, time embedding, sampler step, pooling, tiled-decode
+glue) are checked the same way, each from its operands as they were BEFORE the launch (every tensor argument is copied first:
+several of them write in place), and each also checks that what the launch must not write is unchanged.
+
+GroupNorm statistics.  Of one (image, group) of n = HW * cpg fp16 values, from the STORED tensors (both sources of a fused
+concat).  The kernels sum x and x^2 in fp32 (32-row slabs of the producer epilogue, or the row chunks of the standalone
+statistics pass: at most 33 roundings each, stats_check), combine the partials in a fixed order (<= n terms) and take the
+one-pass variance var = q / n - mean^2 in fp32.  With Q = q / n = var + mean^2:
+
+    E_mean = A(n) U mean|x| + 2 U |mean|                      A(n) = 33 + C_ACC sqrt(n)
+    E_var  = (A(n) + 1 + ONE_PASS_C) U Q + 2 |mean| E_mean + E_mean^2      ONE_PASS_C = 3 (q / n, mean^2, the subtraction)
+
+Q = kappa (var + eps): the error of the variance relative to what rstd = rsqrt(var + eps) sees grows with
+kappa = (var + mean^2) / (var + eps).  rstd is off by rel_r (the perturbed-variance form of _ln_product, + 4 U for rsqrtf);
+scale = gamma rstd is off by |scale| (rel_r + U), shift = beta - mean scale by |mean| E_scale + |scale| E_mean + 2 U (|mean
+scale| + |shift|).  The apply pass adds one fma rounding and the SiLU (exp2 / rcp approximations: 8 U |v|, slope <= 1.1).
+
+Tripwire.  The one-pass term alone, (ONE_PASS_STAT + ONE_PASS_C) U kappa relative to var + eps (the slab sum of squares and
+the three roundings at the magnitude Q), moves rstd by half that and so the normalised output by half that relative to
+itself.  A quarter of an fp16 ulp is at least 2^-13 relative, hence every GroupNorm launch must keep
+
+    kappa <= KAPPA_TRIP = 2^-12 / ((ONE_PASS_STAT + ONE_PASS_C) U) = 2^12 / 36 ~= 114
+
+beyond which the variance must be computed without cancellation (slab (count, mean, M2) combined in Chan's form).
+
+LayerNorm (two-pass, one wave per row): E_mean = C_ACC sqrt(C) U mean|x| + U |mean|; centred on the kernel's mean the sum of
+squares gains exactly C E_mean^2 (the cross term vanishes about the exact mean), so E_var = (C_ACC sqrt(C) + 4) U var +
+E_mean^2; rstd as above; (x - mean) rstd gamma + beta adds E_mean rstd |gamma| and four roundings per element.
+Row softmax: exp of a fp32 difference (relative error U |v - m| + 2 U, __expf), an fp32 sum of n positive terms
+(C_ACC sqrt(n) U), a reciprocal and a product: relative error (2 max|v - m| + C_ACC sqrt(n) + 8) U, then the fp16 store;
+padding columns written as exact zeros.  Gathers (transpose, token + position embedding) are exact: the embedding adds two
+fp16 values in fp32 and rounds once, which IS the reference fl16(fl32(a + b)).  Time embedding: the argument t 10000^(-k/half)
+is formed in fp32 from exp of a rounded exponent: relative error (3 |ln(10^4) k / half| + 4) U, i.e. an absolute error of
+that times |t f| in the argument; cos / sin add 4 U; then the fp16 store.  Sampler step: one rounding per operation, each
+bounded by U times the magnitude it produces (sampler_step_reference), never relative to the result (x0 divides by
+sqrt(alpha_t) ~ 0.07 at t = 999).  latents_pool8: L-term fp32 bin sums, (L + 1) U mean|x| before the fp16 store.
+vae_blend: 4 U (|a| + |b|).  vae_place_tile: the fp32 copy is exact, the u8 value is round-half-even(clamp(v/2 + 1/2) 255)
+except within 4 U 255 of a .5 tie, where either neighbour is accepted (and counted).
 """
 from __future__ import annotations
 
 import inspect
 import math
 
+import numpy as np
 import torch
 
 U = 2.0 ** -24          # fp32 unit roundoff
@@ -38,6 +78,9 @@ C_ACC = 8.0             # multiple of sqrt(K) * U * S allowed for fp32 accumulat
 GELU_APPROX = 1e-7      # |gelu_erf_f(x) - gelu(x)| / |x|: Abramowitz-Stegun 7.1.26 erf (|err| <= 1.5e-7) times x / 2
 BAND_BYTES = 1 << 30    # working set of one im2col band (three fp64 copies of it live at once)
 LN2 = math.log(2.0)
+ONE_PASS_STAT = 33      # roundings of one fp32 slab sum of squares (stats_check)
+ONE_PASS_C = 3          # q / n, mean^2 and their difference, all at the magnitude Q = var + mean^2
+KAPPA_TRIP = 2.0 ** -12 / ((ONE_PASS_STAT + ONE_PASS_C) * U)     # ~= 113.8 (module docstring)
 
 
 def acc_err(K, S):
@@ -57,6 +100,22 @@ def worst_ratio(got, ref, bound):
     r = (g - ref).abs() / bound
     r = torch.where(torch.isfinite(g), r, torch.full_like(r, math.inf))
     return float(r.max()) if r.numel() else 0.0
+
+
+def same_bits(a, b):
+    """bit-identical (NaN payloads of never-written scratch compare equal to themselves)."""
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    if a.is_floating_point():
+        it = {2: torch.int16, 4: torch.int32, 8: torch.int64}[a.element_size()]
+        a, b = a.view(it), b.view(it)
+    return torch.equal(a, b)
+
+
+def tail_same(after, before, n):
+    """the elements of ``after`` past the first n (flattened) are those of ``before``: a launch that writes a logical prefix
+    of a larger buffer must leave the rest of it alone."""
+    return same_bits(after.reshape(-1)[n:], before.reshape(-1)[n:])
 
 
 def _f64(t, dev):
@@ -359,9 +418,266 @@ def stats_check(stats, out, n_images):
     return float(r.max())
 
 
+# ---- GroupNorm / LayerNorm ---------------------------------------------------------------------------------------------
+def _rel_rstd(v, E_var, eps):
+    """relative error of rsqrtf(var' + eps) with |var' - var| <= E_var, v = var + eps (fp64)."""
+    return torch.sqrt(v / torch.clamp(v - E_var, min=eps)) - 1.0 + 4 * U
+
+
+def gn_group_stats(xs, b, HW, groups):
+    """fp64 statistics of image b of the concat of the fp16 sources ``xs`` ([B*HW, Ci] each) -> (x [HW, C] fp64, mean, var,
+    Q = E[x^2], mean|x|) per group, n = HW * C / groups."""
+    x = torch.cat([s[b * HW:(b + 1) * HW].to(torch.float64) for s in xs], 1)
+    g = x.reshape(HW, groups, -1)
+    mean = g.mean((0, 2))
+    var = ((g - mean[None, :, None]) ** 2).mean((0, 2))
+    return x, mean, var, (g * g).mean((0, 2)), g.abs().mean((0, 2))
+
+
+def gn_tables_reference(mean, var, Q, amean, n, gamma, beta, eps):
+    """(scale, shift) [C] fp64 of one image with their error bounds and kappa per group (module docstring)."""
+    A = 33 + C_ACC * math.sqrt(n)
+    E_mean = A * U * amean + 2 * U * mean.abs()
+    E_var = (A + 1 + ONE_PASS_C) * U * Q + 2 * mean.abs() * E_mean + E_mean * E_mean
+    v = var + eps
+    rel_r = _rel_rstd(v, E_var, eps)
+    cpg = gamma.numel() // mean.numel()
+    r = lambda t: t.repeat_interleave(cpg)
+    g, bt = gamma.to(torch.float64), beta.to(torch.float64)
+    scale = g / torch.sqrt(r(v))
+    shift = bt - r(mean) * scale
+    E_scale = scale.abs() * (r(rel_r) + U)
+    E_shift = r(mean).abs() * E_scale + scale.abs() * r(E_mean) + 2 * U * ((r(mean) * scale).abs() + shift.abs())
+    return scale, shift, E_scale + 1e-38, E_shift + 1e-38, Q / v
+
+
+def gn_apply_reference(x, scale, shift, E_scale, E_shift, silu):
+    """y = act(x scale + shift) of one image (x [HW, C] fp64) -> (ref, bound) for the fp16 output."""
+    v = x * scale + shift
+    E = x.abs() * E_scale + E_shift + U * v.abs()
+    if silu:
+        y = v * torch.sigmoid(v)
+        E = 1.1 * E + 8 * U * v.abs()
+    else:
+        y = v
+    return y, store_bound(y, E)
+
+
+def gn_check(got_scale, got_shift, xs, B, HW, groups, gamma, beta, eps, *, out=None, silu=True, images=None):
+    """Worst ratio of the tables (and of the applied output ``out`` [B*HW, C] if given) of a GroupNorm launch, worst kappa."""
+    C = sum(s.shape[1] for s in xs)
+    n = HW * (C // groups)
+    worst, kap = 0.0, 0.0
+    for b in (range(B) if images is None else images):
+        x, mean, var, Q, amean = gn_group_stats(xs, b, HW, groups)
+        sc, sh, Es, Eh, k = gn_tables_reference(mean, var, Q, amean, n, gamma.to(x.device), beta.to(x.device), eps)
+        kap = max(kap, float(k.max()))
+        if got_scale is not None:
+            worst = max(worst, worst_ratio(got_scale[b], sc, Es), worst_ratio(got_shift[b], sh, Eh))
+        if out is not None:
+            ref, bnd = gn_apply_reference(x, sc, sh, Es, Eh, silu)
+            worst = max(worst, worst_ratio(out[b * HW:(b + 1) * HW], ref, bnd))
+    return worst, kap
+
+
+def layernorm_reference(x, gamma, beta, eps):
+    """two-pass LayerNorm of fp16 rows x [M, C] -> (ref, bound) fp64."""
+    X = x.to(torch.float64)
+    C = X.shape[1]
+    mean = X.mean(1, keepdim=True)
+    d = X - mean
+    var = (d * d).mean(1, keepdim=True)
+    E_mean = C_ACC * math.sqrt(C) * U * X.abs().mean(1, keepdim=True) + U * mean.abs()
+    E_var = (C_ACC * math.sqrt(C) + 4) * U * var + E_mean * E_mean
+    v = var + eps
+    rel_r = _rel_rstd(v, E_var, eps)
+    g, bt = gamma.to(x.device, torch.float64), beta.to(x.device, torch.float64)
+    rstd = 1.0 / torch.sqrt(v)
+    core = d * rstd * g
+    y = core + bt
+    E = (E_mean + U * d.abs()) * rstd * g.abs() + core.abs() * (rel_r + 2 * U) + U * (y.abs() + bt.abs())
+    return y, store_bound(y, E)
+
+
+# ---- row softmax, gathers, time embedding --------------------------------------------------------------------------------
+def softmax_reference(x, n):
+    """softmax over the first n columns of fp16 rows x [R, ld] -> (ref [R, n], bound)."""
+    X = x[:, :n].to(torch.float64)
+    m = X.max(1, keepdim=True).values
+    P = torch.softmax(X, 1)
+    spread = (X - m).abs()
+    rel = (spread + 2 * spread.max(1, keepdim=True).values + C_ACC * math.sqrt(n) + 8) * U
+    return P, store_bound(P, rel * P)
+
+
+def embed_reference(ids, tok, pos, B, S):
+    """CLIP token + position embedding, ids clamped to the vocabulary: fl16(fl32(tok + pos)) (exact: one rounding)."""
+    idx = ids.reshape(-1).long().clamp(0, tok.shape[0] - 1)
+    p = pos[:S].repeat(B, 1)
+    return (tok[idx].to(torch.float64) + p.to(torch.float64)).to(torch.float32).to(torch.float16)
+
+
+def timestep_reference(ts, B, dim, half_exp=None):
+    """rows step-major [len(ts) * B, dim]: cos | sin of t 10000^(-k / half) -> (ref, bound).  half_exp: the exponent's
+    denominator (default half; the CPU self-test passes a wrong one)."""
+    half = dim // 2
+    k = torch.arange(half, dtype=torch.float64)
+    expo = math.log(10000.0) * k / (half if half_exp is None else half_exp)
+    f = torch.exp(-expo)
+    t = torch.tensor([float(np.float32(v)) for v in ts], dtype=torch.float64).repeat_interleave(B)[:, None]
+    a = t * f[None, :]
+    Ea = a.abs() * (3 * expo + 4)[None, :] * U
+    ref = torch.cat([torch.cos(a), torch.sin(a)], 1)
+    E = torch.cat([Ea, Ea], 1) + 4 * U
+    return ref, store_bound(ref, E)
+
+
+# ---- sampler step --------------------------------------------------------------------------------------------------------
+def sampler_step_reference(m, lat, noise, coef6, last, *, m_u=None, guidance=1.0, pred="epsilon"):
+    """LCMScheduler.step in fp64 from the fp32 operands: m / m_u NHWC [B, h, w, 4] model output(s), lat / noise NCHW, coef6 as
+    the kernel receives them (fp32) -> (new lat NCHW, bound).  Every rounding is bounded by U times the magnitude of what that
+    operation produces (the terms, not the result: the epsilon form divides by sqrt(alpha_t))."""
+    c = [float(np.float32(v)) for v in coef6]
+    sa, sb, c_skip, c_out, sap, sbp = c
+    M = m.to(torch.float64).permute(0, 3, 1, 2)
+    X = lat.to(torch.float64)
+    if m_u is not None:
+        Mu = m_u.to(torch.float64).permute(0, 3, 1, 2)
+        g = float(np.float32(guidance))
+        d = M - Mu
+        M = Mu + g * d
+        E_m = U * (d.abs() + 2 * abs(g) * d.abs() + M.abs())
+    else:
+        E_m = torch.zeros_like(M)
+    if pred == "epsilon":
+        num = X - sb * M
+        E_num = sb * E_m + U * (sb * M.abs() + num.abs())
+        x0 = num / sa
+        E_x0 = E_num / sa + 2 * U * x0.abs()
+    elif pred == "v_prediction":
+        x0 = sa * X - sb * M
+        E_x0 = sb * E_m + 2 * U * (sa * X.abs() + sb * M.abs()) + U * x0.abs()
+    else:
+        x0, E_x0 = M, E_m
+    den = c_out * x0 + c_skip * X
+    E = abs(c_out) * E_x0 + 2 * U * (abs(c_out * 1.0) * x0.abs() + abs(c_skip) * X.abs()) + U * den.abs()
+    if last:
+        return den, 2 * E + 1e-38
+    N = noise.to(torch.float64)
+    out = sap * den + sbp * N
+    E = abs(sap) * E + 2 * U * (abs(sap) * den.abs() + abs(sbp) * N.abs()) + U * out.abs()
+    return out, 2 * E + 1e-38
+
+
+# ---- latents preview pooling, tiled-decode glue --------------------------------------------------------------------------
+def pool8_bins(n):
+    """adaptive_avg_pool2d bins of an n-long side into 8: [floor(o n / 8), ceil((o + 1) n / 8))."""
+    return [(o * n // 8, -(-(o + 1) * n // 8)) for o in range(8)]
+
+
+def pool8_reference(lat, bins_h=None, bins_w=None):
+    """lat fp32 [B, 4, h, w] -> (ref [B, 4, 8, 8], bound) for the fp16 output."""
+    L = lat.to(torch.float64)
+    bh, bw = bins_h or pool8_bins(L.shape[2]), bins_w or pool8_bins(L.shape[3])
+    ref = torch.empty(L.shape[0], 4, 8, 8, dtype=torch.float64, device=L.device)
+    E = torch.empty_like(ref)
+    for oy, (y0, y1) in enumerate(bh):
+        for ox, (x0, x1) in enumerate(bw):
+            blk = L[:, :, y0:y1, x0:x1]
+            cnt = (y1 - y0) * (x1 - x0)
+            ref[:, :, oy, ox] = blk.mean((2, 3))
+            E[:, :, oy, ox] = (cnt + 1) * U * blk.abs().mean((2, 3))
+    return ref, store_bound(ref, E)
+
+
+def blend_reference(a, b, extent, vertical):
+    """diffusers blend_v / blend_h of tile a into the first ``extent`` rows / columns of tile b (fp32 [B, h, w, 3])
+    -> (b after, bound on the band, band mask)."""
+    A, Bt = a.to(torch.float64), b.to(torch.float64)
+    out = Bt.clone()
+    dev = Bt.device
+    t = torch.arange(extent, dtype=torch.float64, device=dev) / extent
+    if vertical:
+        av, bv = A[:, A.shape[1] - extent:], Bt[:, :extent]
+        out[:, :extent] = av * (1 - t[None, :, None, None]) + bv * t[None, :, None, None]
+    else:
+        av, bv = A[:, :, A.shape[2] - extent:], Bt[:, :, :extent]
+        out[:, :, :extent] = av * (1 - t[None, None, :, None]) + bv * t[None, None, :, None]
+    bnd = torch.full_like(out, 1e-38)
+    band = torch.zeros_like(out, dtype=torch.bool)
+    if vertical:
+        bnd[:, :extent] = 4 * U * (av.abs() + bv.abs()) + 1e-38
+        band[:, :extent] = True
+    else:
+        bnd[:, :, :extent] = 4 * U * (av.abs() + bv.abs()) + 1e-38
+        band[:, :, :extent] = True
+    return out, bnd, band
+
+
+def rgb8_reference(v):
+    """fp32 image values -> (u8 round-half-even(clamp(v/2 + 1/2, 0, 1) 255) as int64, mask of near-ties)."""
+    r = torch.clamp(v.to(torch.float64) * 0.5 + 0.5, 0.0, 1.0) * 255.0
+    u8 = torch.round(r)
+    tie = ((r - torch.floor(r)) - 0.5).abs() <= 4 * U * 255.0
+    return u8.to(torch.int64), tie
+
+
+def rgb8_check(got_u8, v):
+    """-> (number of pixels off by more than the tie allowance, number of near-tie pixels off by one)."""
+    ref, tie = rgb8_reference(v)
+    d = (got_u8.to(ref.device, torch.int64) - ref).abs()
+    return int(((d > 0) & ~tie).sum() + (d > 1).sum()), int(((d == 1) & tie).sum())
+
+
+def tiled_glue_reference(tiles, sample, H, W, overlap=0.25):
+    """diffusers AutoencoderKL.tiled_decode glue from the decoded tiles {(i, j): fp32 [B, th, tw, 3]} (tile order: rows of
+    tiles top to bottom): blend above, then left, with the already-blended neighbours; extent = min(a, b, extent); each tile
+    cropped to ``limit`` and the rows concatenated -> (image fp64 [B, H, W, 3], bound)."""
+    extent = int(sample * overlap)
+    limit = sample - extent
+    ni = 1 + max(i for i, _ in tiles)
+    nj = 1 + max(j for _, j in tiles)
+    res = {k: t.to(torch.float64) for k, t in tiles.items()}
+    err = {k: torch.zeros_like(t) for k, t in res.items()}
+    rows = []
+    for i in range(ni):
+        cols = []
+        for j in range(nj):
+            t, e = res[(i, j)], err[(i, j)]
+            for vertical, nb in ((True, (i - 1, j)), (False, (i, j - 1))):
+                if min(nb) < 0:
+                    continue
+                a, ea = res[nb], err[nb]
+                ext = min(a.shape[1 if vertical else 2], t.shape[1 if vertical else 2], extent)
+                new, bnd, band = blend_reference(a, t, ext, vertical)
+                w = torch.arange(ext, dtype=torch.float64, device=t.device) / ext
+                if vertical:
+                    ws = (1 - w)[None, :, None, None]
+                    e = e.clone()
+                    e[:, :ext] = ea[:, a.shape[1] - ext:] * ws + e[:, :ext] * (1 - ws)
+                else:
+                    ws = (1 - w)[None, None, :, None]
+                    e = e.clone()
+                    e[:, :, :ext] = ea[:, :, a.shape[2] - ext:] * ws + e[:, :, :ext] * (1 - ws)
+                t, e = new, e + torch.where(band, bnd, torch.zeros_like(bnd))
+            res[(i, j)], err[(i, j)] = t, e
+            cols.append((t[:, :limit, :limit], e[:, :limit, :limit]))
+        rows.append((torch.cat([c[0] for c in cols], 2), torch.cat([c[1] for c in cols], 2)))
+    img = torch.cat([r[0] for r in rows], 1)[:, :H, :W]
+    E = torch.cat([r[1] for r in rows], 1)[:, :H, :W]
+    return img, E + 1e-38
+
+
 # ---- the hook ----------------------------------------------------------------------------------------------------------
 HOOKED = ("gemm", "gemm_ln", "mlp_geglu", "conv3x3", "conv3x3_gn", "conv3x3_smalln", "conv3x3_c4", "linear_rows",
           "linear_smallm", "attention")
+# the other entry points of a pass -> the arguments each one writes (all others must come out of the launch unchanged);
+# "ws" is scratch of the standalone GroupNorm forms (partials + tables: any of it may change)
+CHECKED = {"groupnorm_tables_from_stats": ("ws",), "groupnorm": ("out", "ws"), "groupnorm_from_stats": ("out", "ws"),
+           "layernorm": ("out",), "softmax_rows": ("x",), "transpose": ("out",), "embed_tokens": ("out",),
+           "timestep_embedding": ("out",), "timestep_embedding_steps": ("out",), "scheduler_step": ("lat",),
+           "latents_pool8": ("out",), "vae_blend": ("b",), "vae_place_tile": ("out_u8", "out_f32")}
+GN_ENTRIES = ("groupnorm_tables_from_stats", "groupnorm", "groupnorm_from_stats")
 
 
 def _pick_images(n, limit):
@@ -377,7 +693,7 @@ def _ident(k, v):
     """what identifies a launch's shape: tensor shapes / strides, flags, scalars (not the data, not the statistics buffer)"""
     if torch.is_tensor(v):
         return k, tuple(v.shape), tuple(v.stride())
-    if k == "stats":
+    if k in ("stats", "st1", "st2"):
         return k, v is not None
     return k, v if isinstance(v, (int, float, bool, str, type(None))) else repr(v)
 
@@ -394,11 +710,12 @@ class Audit:
         self.checks = []
         self.seen = set()
         self.recs = None
+        self.stats_src = {}                  # id(ops.Stats) -> the [rows, C] tensor whose statistics it holds (last producer)
 
     def __enter__(self):
         from sdlcm_amd import ops
         self._ops = ops
-        self._saved = {n: getattr(ops, n) for n in HOOKED}
+        self._saved = {n: getattr(ops, n) for n in HOOKED + tuple(CHECKED)}
         for n, f in self._saved.items():
             setattr(ops, n, self._wrap(n, f))
         self._rec_cm = ops.recording()
@@ -424,10 +741,16 @@ class Audit:
             ba = sig.bind(*args, **kw)
             ba.apply_defaults()
             A = dict(ba.arguments)
+            if A.get("stats") is not None:
+                self.stats_src[id(A["stats"])] = self._stats_tensor(name, A)
             ident = (name,) + tuple(_ident(k, v) for k, v in A.items())
+            if name in GN_ENTRIES:          # every layer once (its statistics differ, not only its shape)
+                ident += (A["gamma"].data_ptr(),)
             if ident in self.seen:
                 return real(*args, **kw)
             self.seen.add(ident)
+            if name in CHECKED:
+                return self._launch_checked(name, real, args, kw, A)
             out = A["out"]
             keep = {}
             for k, v in A.items():        # whatever the launch may overwrite: inputs sharing the output's storage
@@ -443,6 +766,31 @@ class Audit:
             del keep, A
             return r
         return hooked
+
+    @staticmethod
+    def _stats_tensor(name, A):
+        out = A["out"]
+        if name == "gemm" and A["batch"] == 1 and (A["ldo"] is not None or A["N"] is not None):
+            M = A["M"] if A["M"] is not None else A["a"].shape[0]
+            N = A["N"] if A["N"] is not None else A["w"].shape[0]
+            return out.as_strided((M, N), (A["ldo"] if A["ldo"] is not None else out.stride(-2), 1), out.storage_offset())
+        return out
+
+    def _launch_checked(self, name, real, args, kw, A):
+        before = {k: v.clone() for k, v in A.items() if torch.is_tensor(v)}
+        r = real(*args, **kw)
+        torch.cuda.current_stream().synchronize()
+        after = {k: v for k, v in A.items() if torch.is_tensor(v)}
+        for k, v in after.items():                       # what the launch must not write
+            if k not in CHECKED[name]:
+                assert same_bits(v, before[k]), f"{name}: operand {k} changed by the launch"
+        B = dict(A)
+        B.update(before)
+        self._note = {}
+        ratio, kappa = getattr(self, "_ref_" + name)(B, A, r)
+        self.checks.append(dict(op=name, key=None, entry=None, config=None, ratio=ratio, stats_ratio=None, kappa=kappa,
+                                **self._note))
+        return r
 
     def _config(self, key, meta):
         if key is None:
@@ -588,6 +936,115 @@ class Audit:
         return attention_check(A["out"], A["q"], A["k"], A["v"], A["B"], A["heads"], A["Sq"], A["Sk"], d, scale=scale,
                                causal=A["causal"], images=_pick_images(A["B"], self.images)), None
 
+    # -- the other entry points: (B = operands before the launch, A = the live arguments after it, r = what it returned)
+    #    -> (worst ratio, worst GroupNorm kappa or None)
+    def _gn_sources(self, st, C):
+        t = self.stats_src.get(id(st))
+        assert t is not None, "GroupNorm statistics whose producing launch the audit did not see"
+        assert t.shape[1] == C, f"statistics source has {t.shape[1]} channels, the launch {C}"
+        return t
+
+    def _ref_groupnorm_tables_from_stats(self, B, A, r):
+        Bn, HW, C1 = A["B"], A["HW"], A["C1"]
+        st2 = A["st2"]
+        xs = [self._gn_sources(A["st1"], C1)] + ([self._gn_sources(st2, A["C2"])] if st2 is not None else [])
+        C = sum(x.shape[1] for x in xs)
+        ws, ws0 = A["ws"], B["ws"]
+        assert same_bits(ws[2 * Bn * C:], ws0[2 * Bn * C:]), "groupnorm_tables_from_stats wrote past its tables"
+        scale, shift = r
+        return gn_check(scale, shift, xs, Bn, HW, A["groups"], A["gamma"], A["beta"], A["eps"],
+                        images=_pick_images(Bn, self.images))
+
+    def _gn_out(self, B, A, silu):
+        xs = [B["x"]] + ([B["x2"]] if B.get("x2") is not None else [])
+        C = sum(x.shape[1] for x in xs)
+        Bn, HW = A["B"], A["HW"]
+        xs = [x[:Bn * HW] for x in xs]
+        assert tail_same(A["out"], B["out"], Bn * HW * C), "groupnorm wrote past its B * HW rows"
+        return gn_check(None, None, xs, Bn, HW, A["groups"], A["gamma"], A["beta"], A["eps"], out=A["out"].reshape(-1, C),
+                        silu=silu, images=_pick_images(Bn, self.images))
+
+    def _ref_groupnorm(self, B, A, r):
+        return self._gn_out(B, A, A["silu"])
+
+    def _ref_groupnorm_from_stats(self, B, A, r):
+        return self._gn_out(B, A, A["silu"])
+
+    def _ref_layernorm(self, B, A, r):
+        M, C = A["M"], A["C"]
+        assert tail_same(A["out"], B["out"], M * C), "layernorm wrote past its M rows"
+        ref, bnd = layernorm_reference(B["x"].reshape(-1, C)[:M], B["gamma"], B["beta"], A["eps"])
+        return worst_ratio(A["out"].reshape(-1, C)[:M], ref, bnd), None
+
+    def _ref_softmax_rows(self, B, A, r):
+        rows, n, ld = A["rows"], A["n"], A["ld"]
+        x0, x = B["x"].reshape(-1)[:rows * ld].view(rows, ld), A["x"].reshape(-1)[:rows * ld].view(rows, ld)
+        assert not x[:, n:].any(), "softmax_rows: padding columns not zeroed"
+        assert tail_same(A["x"], B["x"], rows * ld), "softmax_rows wrote past its rows"
+        ref, bnd = softmax_reference(x0, n)
+        return worst_ratio(x[:, :n], ref, bnd), None
+
+    def _ref_transpose(self, B, A, r):
+        R, Cc, nb = A["R"], A["Cc"], A["batch"]
+        x, out0, out = B["x"], B["out"], A["out"]
+        iv = x.as_strided((nb, R, Cc), (A["stride_in"], A["ldi"], 1), x.storage_offset())
+        exp = out0.clone()
+        exp.as_strided((nb, Cc, R), (A["stride_out"], A["ldo"], 1), exp.storage_offset()).copy_(iv.transpose(1, 2))
+        return (0.0 if same_bits(out, exp) else math.inf), None
+
+    def _ref_embed_tokens(self, B, A, r):
+        Bn, S, D = A["B"], A["S"], A["D"]
+        ref = embed_reference(B["ids"], B["tok_emb"], B["pos_emb"], Bn, S)
+        assert tail_same(A["out"], B["out"], Bn * S * D), "embed_tokens wrote past its B * S rows"
+        return (0.0 if torch.equal(A["out"].reshape(-1, D)[:Bn * S], ref) else math.inf), None
+
+    def _temb(self, ts, B, A):
+        Bn, dim = A["B"], A["dim"]
+        assert tail_same(A["out"], B["out"], len(ts) * Bn * dim), "timestep embedding wrote past its rows"
+        ref, bnd = timestep_reference(ts, Bn, dim)
+        dev = A["out"].device
+        return worst_ratio(A["out"].reshape(-1, dim)[:len(ts) * Bn], ref.to(dev), bnd.to(dev)), None
+
+    def _ref_timestep_embedding(self, B, A, r):
+        return self._temb([A["t"]], B, A)
+
+    def _ref_timestep_embedding_steps(self, B, A, r):
+        return self._temb(list(A["ts"]), B, A)
+
+    def _ref_scheduler_step(self, B, A, r):
+        ref, bnd = sampler_step_reference(B["eps"], B["lat"], B.get("noise"), A["coef6"], A["last"], m_u=B.get("eps_uncond"),
+                                          guidance=A["guidance"], pred=A["pred"])
+        return worst_ratio(A["lat"], ref, bnd), None
+
+    def _ref_latents_pool8(self, B, A, r):
+        Bn, h, w = A["B"], A["h"], A["w"]
+        ref, bnd = pool8_reference(B["lat"].reshape(-1)[:Bn * 4 * h * w].view(Bn, 4, h, w))
+        assert tail_same(A["out"], B["out"], Bn * 256), "latents_pool8 wrote past its B x 4 x 8 x 8 values"
+        return worst_ratio(A["out"].reshape(-1)[:Bn * 256].view(Bn, 4, 8, 8), ref, bnd), None
+
+    def _ref_vae_blend(self, B, A, r):
+        Bn = A["B"]
+        a = B["a"].reshape(Bn, A["ah"], A["aw"], 3)
+        b0, b = B["b"].reshape(Bn, A["bh"], A["bw"], 3), A["b"].reshape(Bn, A["bh"], A["bw"], 3)
+        ref, bnd, band = blend_reference(a, b0, A["extent"], A["vertical"])
+        assert same_bits(b[~band], b0[~band]), "vae_blend wrote outside its band"
+        return worst_ratio(b, ref, bnd), None
+
+    def _ref_vae_place_tile(self, B, A, r):
+        Bn, H, W, oy, ox, ch, cw = A["B"], A["H"], A["W"], A["oy"], A["ox"], A["ch"], A["cw"]
+        tile = B["tile"].reshape(Bn, A["th"], A["tw"], 3)[:, :ch, :cw]
+        crop = torch.zeros(Bn, H, W, 3, dtype=torch.bool, device=tile.device)
+        crop[:, oy:oy + ch, ox:ox + cw] = True
+        u8, u80 = A["out_u8"].reshape(Bn, H, W, 3), B["out_u8"].reshape(Bn, H, W, 3)
+        assert torch.equal(u8[~crop], u80[~crop]), "vae_place_tile wrote u8 pixels outside its crop"
+        bad, ties = rgb8_check(u8[:, oy:oy + ch, ox:ox + cw], tile)
+        self._note["ties"] = ties                   # near-tie u8 pixels off by one: allowed, counted
+        ok = bad == 0
+        if A["out_f32"] is not None:
+            f, f0 = A["out_f32"].reshape(Bn, H, W, 3), B["out_f32"].reshape(Bn, H, W, 3)
+            ok = ok and same_bits(f[~crop], f0[~crop]) and same_bits(f[:, oy:oy + ch, ox:ox + cw], tile)
+        return (0.0 if ok else math.inf), None
+
 
 def config_table(checks):
     """rows (kind, bm, bn, splits, variant) -> [launches checked, worst ratio, worst statistics ratio]."""
@@ -601,3 +1058,33 @@ def config_table(checks):
         if c["stats_ratio"] is not None:
             r[2] = max(r[2], c["stats_ratio"])
     return rows
+
+
+def entry_table(checks):
+    """entry point -> [launches checked, worst ratio, worst GroupNorm kappa (0 if none)]."""
+    rows = {}
+    for c in checks:
+        r = rows.setdefault(c["op"], [0, 0.0, 0.0])
+        r[0] += 1
+        r[1] = max(r[1], c["ratio"])
+        if c.get("kappa") is not None:
+            r[2] = max(r[2], c["kappa"])
+    return rows
+
+
+def failures(checks):
+    """launches outside their bound, statistics outside theirs, or GroupNorm launches past the kappa tripwire."""
+    return [c for c in checks if not (c["ratio"] <= 1.0) or (c["stats_ratio"] is not None and not (c["stats_ratio"] <= 1.0))
+            or (c.get("kappa") is not None and not (c["kappa"] <= KAPPA_TRIP))]
+
+
+def summary_line(checks):
+    worst_k = max((c.get("kappa") or 0.0) for c in checks) if checks else 0.0
+    per = ", ".join(f"{op} {n}/{r:.3f}" for op, (n, r, _) in sorted(entry_table(checks).items()))
+    ties = [c["ties"] for c in checks if "ties" in c]
+    return (f"worst ratio {max((c['ratio'] for c in checks), default=0.0):.3f}, "
+            f"worst statistics ratio {max(((c['stats_ratio'] or 0.0) for c in checks), default=0.0):.3f}, "
+            f"worst GroupNorm kappa {worst_k:.4g} (tripwire {KAPPA_TRIP:.4g})"
+            + (f", u8 near-ties off by one {sum(ties)} over {len(ties)} placed tiles" if ties else "")
+            + f"; checked/worst per entry: {per}")
+

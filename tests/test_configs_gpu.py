@@ -212,19 +212,29 @@ def _audit_pass(hip, name, B, size, guidance=1.0, **kw):
     launched = au.record_keys()
     _AUDITED[name] = (au.checks, launched)
     assert au.checked_keys() == launched, f"{name}: hook saw {len(au.checked_keys())} of {len(launched)} plan keys"
-    bad = [c for c in au.checks if not (c["ratio"] <= 1.0) or (c["stats_ratio"] is not None and not (c["stats_ratio"] <= 1.0))]
-    print(f"[audit] {name}: {len(au.checks)} launches checked, {len(launched)} plan keys "
-          f"({sum(k in au.table for k in launched)} in the table), worst ratio {max(c['ratio'] for c in au.checks):.3f}, "
-          f"worst statistics ratio {max((c['stats_ratio'] or 0.0) for c in au.checks):.3f}")
-    for c in bad:
-        print(f"[audit] {name} FAIL {c}")
-    assert not bad, f"{name}: {len(bad)} launches outside their fp64 error bound"
+    _audit_verdict(name, au, f"{len(launched)} plan keys ({sum(k in au.table for k in launched)} in the table), ")
     return au
 
 
+def _audit_verdict(name, au, extra=""):
+    from launch_audit import failures, summary_line
+    bad = failures(au.checks)
+    print(f"[audit] {name}: {len(au.checks)} launches checked, {extra}{summary_line(au.checks)}")
+    for c in bad:
+        print(f"[audit] {name} FAIL {c}")
+    assert not bad, f"{name}: {len(bad)} launches outside their fp64 error bound (or past the GroupNorm kappa tripwire)"
+
+
 def _audit_report(table):
-    from launch_audit import config_table
+    from launch_audit import CHECKED, config_table, entry_table
     checks = [c for name in _AUDITED for c in _AUDITED[name][0]]
+    per = entry_table(checks)
+    for op in sorted(per):
+        n, r, k = per[op]
+        print(f"[audit] entry {op:>28}: {n:>5} launches checked, worst ratio {r:.3f}" + (f", worst kappa {k:.4g}" if k else ""))
+    # every entry point the audit checks was reached by a real pass: a refactor that routes around ops.X fails here
+    missing = sorted(set(CHECKED) - set(per))
+    assert not missing, f"audited entry points no pass reached: {missing}"
     reached = set().union(*(v[1] for v in _AUDITED.values()))
     rows = config_table(checks)
     table_cfgs = {(k[0],) + tuple(int(x) for x in v[:4]) for k, v in table.items()}
@@ -247,6 +257,31 @@ def test_audit_sd15_tuned_passes_fp64(sd15):
         _audit_pass(hip, f"sd15 B{B} {size}px", B, size, pe=_embeds(B, seed=60 + B))
 
 
+def test_audit_sd15_text_encoder_and_unfused_paths_fp64(monkeypatch):
+    """The SD1.5 text encoder (CLIP-L, last hidden state) under the audit, and a small SD1.5 pass through the paths the tuned
+    passes do not take: the VAE mid attention on the MFMA GEMMs (scores + softmax_rows + transpose; the flash kernel is the
+    default for 512-wide VAEs) and the time embedding computed per step (time_embed, not time_embed_all)."""
+    from launch_audit import Audit
+    from sdlcm_amd import model, weights
+    from sdlcm_amd.clip import CLIP_L, ClipTextHip, HashTokenizer, synthetic_clip
+    from sdlcm_amd.pipeline import LcmHipPipeline
+    enc = ClipTextHip(synthetic_clip(CLIP_L), CLIP_L, device="cuda:0")
+    with Audit() as au:
+        enc.forward(HashTokenizer()(["a red fox in the snow", "a lighthouse"]))
+    _AUDITED["clip-l"] = (au.checks, set())
+    _audit_verdict("clip-l", au)
+    del enc
+    monkeypatch.setattr(model, "VAE_FLASH_ATTN", False)
+    hip = LcmHipPipeline(weights.synthetic_unet(), weights.synthetic_vae(), device="cuda:0")
+    try:
+        assert not hip.vae.flash_attn
+        monkeypatch.setattr(hip.unet, "MAX_HOISTED_STEPS", 0)
+        _audit_pass(hip, "sd15 B2 128px unfused", 2, 128, pe=_embeds(2, seed=70))
+    finally:
+        hip.close()
+    torch.cuda.empty_cache()
+
+
 def test_audit_sdxl_1024_passes_fp64(sdxl):
     """SDXL 1024x1024 without and with classifier-free guidance (the two SDXL passes of tools/make_plans.py)."""
     hip = sdxl["hip"]
@@ -256,6 +291,19 @@ def test_audit_sdxl_1024_passes_fp64(sdxl):
     neg, neg_pooled = torch.randn(1, 77, 2048, generator=g).half(), torch.randn(1, 1280, generator=g).half()
     _audit_pass(hip, "sdxl B1 1024px cfg", 1, 1024, 5.0, pe=pe, added=(pooled, tids), negative_embeds=neg,
                 negative_added=(neg_pooled, tids))
+    # the SDXL text encoders: CLIP-L and OpenCLIP-bigG penultimate hidden states, bigG's pooled projection
+    from launch_audit import Audit
+    from sdlcm_amd.clip import CLIP_BIGG, CLIP_L, ClipTextHip, HashTokenizer, synthetic_clip
+    ids = HashTokenizer()(["an astronaut riding a horse on the moon"])
+    for cname, cfg, pooled in (("sdxl clip-l", CLIP_L, False), ("sdxl clip-bigg", CLIP_BIGG, True)):
+        enc = ClipTextHip(synthetic_clip(cfg), cfg, device="cuda:0")
+        with Audit() as au:
+            out = enc.forward(ids, output="penultimate", pooled=pooled)
+        assert (out[1].shape == (1, cfg["projection_dim"])) if pooled else (out.shape == (1, 77, cfg["hidden_size"]))
+        _AUDITED[cname] = (au.checks, set())
+        _audit_verdict(cname, au)
+        del enc, out
+        torch.cuda.empty_cache()
     from sdlcm_amd import lib
     _audit_report(lib.known_plans())
 

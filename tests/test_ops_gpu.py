@@ -776,12 +776,13 @@ def test_timestep_embedding_and_step_and_pool():
     ops.scheduler_step(eps.permute(0, 2, 3, 1).contiguous().to(DEV), d, noise.to(DEV), coef[:6], coef[6], B, h, w,
                        eps_uncond=eu.permute(0, 2, 3, 1).contiguous().to(DEV), guidance=7.5)
     close(d, ref, rtol=1e-5, atol=2e-5, what="scheduler step cfg")
+    import launch_audit as la
     for hh, ww in ((64, 64), (96, 64), (8, 8), (12, 20)):
         lt = torch.randn(1, 4, hh, ww, generator=g)
         o = torch.empty(1, 4, 8, 8, dtype=torch.float16, device=DEV)
         ops.latents_pool8(lt.to(DEV), o, 1, hh, ww)
         assert o.cpu().numpy().tobytes() == glue.latents_blob(lt.numpy()) or \
-            np.abs(o.cpu().float().numpy() - np.frombuffer(glue.latents_blob(lt.numpy()), np.float16).reshape(1, 4, 8, 8).astype(np.float32)).max() < 2e-3
+            la.worst_ratio(o.cpu(), *la.pool8_reference(lt)) <= 1.0
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1369,3 +1370,148 @@ def test_axpy_past_grid_stride_span_fp64(in_place):
     ref = base.double().to(DEV) + a32 * delta.double().to(DEV)
     E = 2 * la.U * (base.double().abs().to(DEV) + abs(a32) * delta.double().abs().to(DEV))
     assert la.worst_ratio(out, ref, la.store_bound(ref, E)) <= 1.0
+
+
+# ---- GroupNorm on offset activations, pooling, time embedding and sampler step against fp64 (tests/launch_audit.py) ------
+@pytest.mark.parametrize("offset", [0.0, 3.0, 9.5])
+def test_groupnorm_all_forms_on_offset_activations_fp64(offset):
+    """|mean| / std of every group from 0 to 9.5 (kappa ~1, ~11 and ~102: up to just under the audit's tripwire of ~114):
+    the standalone GroupNorm, the affine tables alone (groupnorm_affine, which no pass launches), and GroupNorm from
+    statistics fused in a conv epilogue (tables only, finalize + apply, and the single-launch form), each against the fp64
+    statistics of the stored tensor.  The reached kappa is asserted from below too, so the case cannot drift back to ~1."""
+    import launch_audit as la
+    B, H, W, Cin, C = 2, 16, 16, 320, 640
+    HW = H * W
+    x = to_nhwc(rnd(B, Cin, H, W, seed=31)).to(DEV)
+    w = pack3x3(rnd(C, Cin, 3, 3, seed=32, scale=(9 * Cin) ** -0.5)).to(DEV)
+    # the conv output has std ~1 per channel; its bias sets |mean| / std.  The sign is constant within a group (20 channels):
+    # a sign flip inside a group would turn the offset into variance between its channels instead of a group mean
+    sign = torch.where((torch.arange(C) // (C // 32)) % 3 == 0, -1.0, 1.0)
+    b = (offset * sign + 0.1 * rnd(C, seed=33).float()).half().to(DEV)
+    out = torch.empty(B * HW, C, dtype=torch.float16, device=DEV)
+    st = ops.Stats(torch.zeros(ops.stats_floats(B * HW, C, HW), dtype=torch.float32, device=DEV))
+    ops.conv3x3(x, w, out, B, H, W, Cin, C, bias=b, stats=st)
+    assert st.P > 0
+    gamma, beta = (1 + 0.1 * rnd(C, seed=34).float()).half().to(DEV), rnd(C, seed=35, scale=0.1).to(DEV)
+    ws = torch.zeros(ops.groupnorm_ws_bytes(B, HW, C) // 4 + 16, dtype=torch.float32, device=DEV)
+    chk = lambda **kw: la.gn_check(kw.pop("sc", None), kw.pop("sh", None), [out], B, HW, 32, gamma, beta, 1e-5, **kw)
+    kap, ratios = [], {}
+    for silu in (True, False):
+        y = torch.empty_like(out)
+        ops.groupnorm(out, gamma, beta, y, B, HW, C, ws, silu=silu)
+        r, k = chk(out=y, silu=silu)
+        ratios[f"groupnorm silu={silu}"] = r
+        kap.append(k)
+        ys = []
+        try:
+            for fused_bytes in (0, 1 << 40):
+                ops.set_gn_fused_bytes(fused_bytes)
+                y = torch.empty_like(out)
+                ops.groupnorm_from_stats(out, gamma, beta, y, B, HW, C, st, ws, silu=silu)
+                ratios[f"groupnorm_from_stats silu={silu} single-launch limit {fused_bytes}"] = chk(out=y, silu=silu)[0]
+                ys.append(y)
+        finally:
+            ops.set_gn_fused_bytes(8 << 20)
+        assert torch.equal(ys[0], ys[1])
+    sc, sh = ops.groupnorm_tables_from_stats(gamma, beta, B, HW, C, st, ws)
+    ratios["groupnorm_tables_from_stats"] = chk(sc=sc.clone(), sh=sh.clone())[0]
+    sc2 = torch.empty(B, C, dtype=torch.float32, device=DEV)
+    sh2 = torch.empty(B, C, dtype=torch.float32, device=DEV)
+    ops.groupnorm_affine(out, gamma, beta, sc2, sh2, B, HW, C, ws)
+    ratios["groupnorm_affine"] = chk(sc=sc2, sh=sh2)[0]
+    print(f"[gn] offset {offset}: kappa {max(kap):.4g} (tripwire {la.KAPPA_TRIP:.4g}); "
+          + ", ".join(f"{k} {v:.3f}" for k, v in ratios.items()))
+    bad = {k: v for k, v in ratios.items() if not v <= 1.0}
+    assert not bad, f"outside the fp64 bound at kappa {max(kap):.4g}: {bad}"
+    assert 0.8 * offset ** 2 <= max(kap) <= la.KAPPA_TRIP
+
+
+@pytest.mark.parametrize("B,h,w", [(1, 13, 9), (2, 100, 97), (3, 7, 23), (1, 1, 1), (2, 96, 64)])
+def test_latents_pool8_ragged_sides_fp64(B, h, w):
+    """adaptive_avg_pool2d bins at sides that are not multiples of 8 (and shorter than 8), every image of the batch."""
+    import launch_audit as la
+    lat = torch.randn(B, 4, h, w, generator=torch.Generator().manual_seed(36)) * 20
+    o = torch.full((B, 4, 8, 8), float("nan"), dtype=torch.float16, device=DEV)
+    ops.latents_pool8(lat.to(DEV), o, B, h, w)
+    assert la.worst_ratio(o.cpu(), *la.pool8_reference(lat)) <= 1.0
+
+
+def test_timestep_embedding_steps_and_sdxl_time_ids_fp64():
+    """Several steps in one launch (rows step-major), and the SDXL added-time-id embedding values (sizes and crops 0..1024)."""
+    import launch_audit as la
+    for ts, B, dim in (([999, 759, 499, 259], 3, 320), ([999, 879, 759, 639, 519, 399, 279, 159], 1, 1280),
+                       ([1024.0, 1024.0, 0.0, 0.0, 1024.0, 1024.0], 1, 256), ([768.0, 1360.0, 17.0, 33.0, 768.0, 1360.0], 2, 256)):
+        out = torch.full((len(ts) * B, dim), float("nan"), dtype=torch.float16, device=DEV)
+        ops.timestep_embedding_steps(ts, out, B, dim)
+        ref, bnd = la.timestep_reference(ts, B, dim)
+        r = la.worst_ratio(out.cpu(), ref, bnd)
+        assert r <= 1.0, (ts, B, dim, r)
+    out = torch.empty(2, 320, dtype=torch.float16, device=DEV)
+    ops.timestep_embedding(999, out, 2, 320)
+    assert la.worst_ratio(out.cpu(), *la.timestep_reference([999], 2, 320)) <= 1.0
+
+
+@pytest.mark.parametrize("pred", ["epsilon", "v_prediction", "sample"])
+@pytest.mark.parametrize("guidance", [None, 7.5])
+def test_scheduler_step_every_prediction_type_fp64(pred, guidance):
+    """LCMScheduler.step for each prediction type, with and without classifier-free guidance, every step of a 4-step
+    schedule (t = 999 first: x0 divides by sqrt(alpha_t) ~ 0.07 in the epsilon form)."""
+    import launch_audit as la
+    from sdlcm_amd.scheduler import LCMSchedule
+    s = LCMSchedule(prediction_type=pred)
+    ts = s.timesteps(4)
+    g = torch.Generator().manual_seed(37)
+    B, h, w = 2, 12, 20
+    m, mu = torch.randn(B, h, w, 4, generator=g), torch.randn(B, h, w, 4, generator=g)
+    lat, noise = torch.randn(B, 4, h, w, generator=g) * 14, torch.randn(B, 4, h, w, generator=g)
+    for i in range(4):
+        coef, last = s.step_coefficients(ts, i)
+        d = lat.to(DEV).clone()
+        kw = dict(eps_uncond=mu.to(DEV), guidance=guidance) if guidance else {}
+        ops.scheduler_step(m.to(DEV), d, noise.to(DEV), coef, last, B, h, w, pred=pred, **kw)
+        ref, bnd = la.sampler_step_reference(m, lat, noise, coef, last, m_u=mu if guidance else None,
+                                             guidance=guidance or 1.0, pred=pred)
+        r = la.worst_ratio(d.cpu(), ref, bnd)
+        assert r <= 1.0, (pred, guidance, i, r)
+
+
+@pytest.mark.parametrize("H,W", [(768, 768), (768, 800), (800, 776)])
+def test_vae_tiled_decode_glue_fp64(H, W):
+    """The tiled decode as a whole: each tile's fp32 output is kept (decode_plain hooked), diffusers' tiled_decode glue is
+    recomputed from those tiles in fp64 (blend above, then left, with already-blended neighbours; extents clipped to the
+    neighbours; crops to ``limit``) and compared with the placed image; the u8 image is the rounding of the fp32 one.
+    Ragged sizes make the last tiles narrower than the blend extent (768 x 800: a 4-latent last column, extent 32 px)."""
+    import launch_audit as la
+    from sdlcm_amd import weights
+    from sdlcm_amd.model import VAEDecoderHip
+    vae = VAEDecoderHip(weights.synthetic_vae(), None, DEV)
+    sample = int(vae.cfg.get("sample_size", 512))
+    h, w = H // 8, W // 8
+    lat = torch.randn(1, 4, h, w, generator=torch.Generator().manual_seed(38)).to(DEV)
+    tiles, order = {}, []
+    real = vae.decode_plain
+
+    def keep(sub, B, th, tw, rgb, img_f32=None, taps=None):
+        r = real(sub, B, th, tw, rgb, img_f32=img_f32, taps=taps)
+        order.append((th, tw))
+        tiles[len(order) - 1] = img_f32.clone()
+        return r
+    vae.decode_plain = keep
+    rgb = torch.zeros(1, H, W, 3, dtype=torch.uint8, device=DEV)
+    img = torch.zeros(1, H, W, 3, dtype=torch.float32, device=DEV)
+    ops.set_workspace(torch.empty(16 << 20, dtype=torch.float32, device=DEV))
+    try:
+        vae.decode(lat, 1, h, w, rgb, img_f32=img)
+        torch.cuda.synchronize()
+    finally:
+        ops.set_workspace(None)
+    stride = int(sample // 8 * 0.75)
+    ys, xs = list(range(0, h, stride)), list(range(0, w, stride))
+    assert order == [(min(sample // 8, h - y), min(sample // 8, w - x)) for y in ys for x in xs], "tile order"
+    grid = {(i, j): tiles[i * len(xs) + j] for i in range(len(ys)) for j in range(len(xs))}
+    ref, E = la.tiled_glue_reference(grid, sample, H, W)
+    assert la.worst_ratio(img, ref, E) <= 1.0
+    bad, ties = la.rgb8_check(rgb, img)
+    print(f"[glue] {H}x{W}: ratio {la.worst_ratio(img, ref, E):.3f}, u8 near-ties off by one {ties}")
+    assert bad == 0, f"{bad} u8 pixels are not the rounding of the fp32 image ({ties} near-ties off by one)"
+

@@ -190,9 +190,10 @@ def _audit(hip, name, pe, guidance=1.0, **kw):
     torch.cuda.empty_cache()
     launched = au.record_keys()
     assert au.checked_keys() == launched, f"{name}: hook saw {len(au.checked_keys())} of {len(launched)} plan keys"
-    bad = [c for c in au.checks if not (c["ratio"] <= 1.0) or (c["stats_ratio"] is not None and not (c["stats_ratio"] <= 1.0))]
+    from launch_audit import failures, summary_line
+    bad = failures(au.checks)
     print(f"[audit] {name}: {len(au.checks)} launches checked, {len(launched)} plan keys "
-          f"({sum(k in au.table for k in launched)} in the table), worst ratio {max(c['ratio'] for c in au.checks):.3f}")
+          f"({sum(k in au.table for k in launched)} in the table), {summary_line(au.checks)}")
     for c in bad:
         print(f"[audit] {name} FAIL {c}")
     assert not bad, f"{name}: {len(bad)} launches outside their fp64 error bound"
@@ -211,9 +212,11 @@ def test_audit_sd2_512_passes_fp64(sd2):
     enc = ClipTextHip(synthetic_clip_h(), CLIP_H, device=DEV)
     with Audit() as au:
         enc.forward(HashTokenizer()(["a castle on a hill at dawn"]))
-    bad = [c for c in au.checks if not (c["ratio"] <= 1.0)]
-    print(f"[audit] clip-h: {len(au.checks)} launches checked, worst ratio {max(c['ratio'] for c in au.checks):.3f}")
+    from launch_audit import failures, summary_line
+    bad = failures(au.checks)
+    print(f"[audit] clip-h: {len(au.checks)} launches checked, {summary_line(au.checks)}")
     assert au.checks and not bad, bad
+    assert {"embed_tokens", "layernorm"} <= {c["op"] for c in au.checks}
 
 
 # ---- 5. the worker -----------------------------------------------------------------------------------------------------
