@@ -375,6 +375,31 @@ int lcm_sr_conv4_shuffle(const void* in, int W, int H, int tile_w, int tile_h, i
 int lcm_sr_chroma_h(const void* rgb, int W, int H, int r, void* cbcr_h, void* stream);
 int lcm_sr_merge(const void* y_plane, const void* cbcr_h, int W, int H, int r, void* rgb_out, void* stream);
 
+/* ---- RGB8 -> baseline JPEG (the ``img.save(buf, format="JPEG", quality=q)`` of the super-resolution worker,
+ * server/lcm_sr_server.py upscale_once): a device front end and a host entropy coder.  4:2:0, 16x16 MCUs, W, H in 1..65535.
+ *   dct_rgb8 (device, one launch, capturable): rgb = H rows of W RGB8 pixels `pitch` bytes apart (any alignment) ->
+ *     coefs int16 [ceil(H/16)][ceil(W/16)][6][64], blocks Y00 Y01 Y10 Y11 Cb Cr, each in zigzag order; coefs is 16-byte
+ *     aligned and coefs_bytes >= lcm_jpeg_coef_bytes(W, H).  Arithmetic: libjpeg's 16-bit fixed point colour conversion
+ *       Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *       Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *       Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16
+ *     chroma = (a + b + c + d + bias) >> 2 over 2x2 with bias 1 for an even output column, 2 for an odd one; the last pixel /
+ *     row replicated up to whole MCUs; level shift -128; fp32 8x8 DCT-II with JPEG normalisation (DC = sum / 8); multiply by
+ *     the fp32 reciprocal of the table entry, round to nearest, clamp DC to +-2047 and AC to +-1023.
+ *   quant_tables: out[0..63] luma, out[64..127] chroma, natural (row-major) order: the Annex K tables scaled as libjpeg's
+ *     jpeg_set_quality(quality, force_baseline = TRUE) does; quality 1..100.
+ *   encode_coefs (host, no GPU work): coefficients of that layout -> a JFIF file: SOI, APP0, two DQT, SOF0, four DHT (the
+ *     Annex K tables), DRI, one interleaved scan, EOI.  The restart interval is one MCU row for every `threads` (rows are
+ *     coded `threads` at a time on the pool the PNG writer owns), so the bytes depend on (coefs, W, H, quality) only.
+ *     out_cap >= lcm_jpeg_bound(W, H).  A DC difference outside +-2047 or an AC value outside +-1023 is LCM_EINVAL. */
+long long lcm_jpeg_coef_bytes(int W, int H);
+long long lcm_jpeg_bound(int W, int H);
+int lcm_jpeg_quant_tables(int quality, uint8_t* out);
+int lcm_jpeg_dct_rgb8(const void* rgb, int W, int H, long long pitch, int quality, void* coefs, long long coefs_bytes,
+                      void* stream);
+int lcm_jpeg_encode_coefs(const void* coefs, int W, int H, int quality, int threads, void* out, long long out_cap,
+                          long long* out_len);
+
 /* ---- hipGraph capture of the 4-step sampler loop + VAE ---- */
 int lcm_graph_begin(void* stream);
 int lcm_graph_end(void* stream, void** graph_exec_out);

@@ -139,6 +139,39 @@ def encode_png(rgb) -> bytes:
             + _png_chunk(b"IDAT", comp) + _png_chunk(b"IEND", b""))
 
 
+_JPEG_ENCODERS = {}
+_JPEG_LOCK = threading.Lock()
+
+
+def encode_jpeg(rgb, quality: int = 92) -> bytes:
+    """uint8 [H,W,3] host pixels -> baseline 4:2:0 JPEG file bytes (the reference's ``img.save(buf, format="JPEG",
+    quality=q)``, server/lcm_sr_server.py): the pixels are uploaded to the current device, ``lcm_jpeg_dct_rgb8``
+    (csrc/jpeg.hip) turns them into quantised coefficients there and ``lcm_jpeg_encode_coefs`` (csrc/jpeg.cpp) writes the file
+    on LCM_JPEG_THREADS host threads (default 8; the bytes do not depend on it).  Callers whose image is already on the device
+    use ``superres.JpegEncoder`` directly.  One encoder per device, one call at a time.  LCM_JPEG_ENCODER=pil: PIL."""
+    if os.environ.get("LCM_JPEG_ENCODER", "").lower() == "pil":
+        from PIL import Image
+        buf = io.BytesIO()
+        Image.fromarray(rgb).save(buf, format="JPEG", quality=int(quality))
+        return buf.getvalue()
+    from .. import superres as _sr
+    q = _sr.check_quality(quality)
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError(f"encode_jpeg expects uint8 [H][W][3], got shape {rgb.shape}")
+    if not torch.cuda.is_available():
+        raise LcmHipError("encode_jpeg needs an MI355X; no CPU fallback exists on this path (LCM_JPEG_ENCODER=pil uses PIL)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    with _JPEG_LOCK:
+        enc = _JPEG_ENCODERS.get(dev)
+        if enc is None:
+            enc = _JPEG_ENCODERS[dev] = _sr.JpegEncoder(dev)
+        stream = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):
+            src = torch.from_numpy(rgb).to(dev)
+        return enc.encode_device(src, q, stream)
+
+
 class _Engine:
     """Everything resident for one (family, device, checkpoint): the pipeline (weights, launch plans, captured graphs), the
     text encoders, the style adapters and the micro-batching dispatcher.  The reference builds one pipeline -- and one

@@ -1,12 +1,14 @@
 """``HipSuperResWorker`` -- the MI355X drop-in for the reference's RKNNLite ``SuperResWorker``
 (server/lcm_sr_server.py:312-405): same constructor and ``upscale_once`` / ``upscale_bytes`` / ``close`` methods, with the tiled
-numpy + NPU loop replaced by the HIP passes of ``superres.SuperResNet`` (csrc/sr.hip).  ``SuperResService`` builds
+numpy + NPU loop replaced by the HIP passes of ``superres.SuperResNet`` (csrc/sr.hip).  ``png`` output is written by
+csrc/png.cpp; ``jpeg`` output by csrc/jpeg.hip + csrc/jpeg.cpp from the image on the device (LCM_JPEG_ENCODER=pil: by PIL).  ``SuperResService`` builds
 SR_NUM_WORKERS of these, each driven from its own thread: every worker has its own stream and workspace.  Install with
 ``server.lcm_sr_server.SuperResWorker = HipSuperResWorker``.  No CPU fallback: without a GPU the constructor
 raises."""
 from __future__ import annotations
 
 import io
+import os
 
 import numpy as np
 import torch
@@ -21,6 +23,11 @@ FORMATS = ("png", "jpeg")
 def _decode(image_bytes: bytes) -> np.ndarray:
     from PIL import Image
     return np.asarray(Image.open(io.BytesIO(image_bytes)).convert("RGB"))
+
+
+def _pil_jpeg() -> bool:
+    """LCM_JPEG_ENCODER=pil: the JPEG file comes from PIL on the host pixels, as before the library wrote it."""
+    return os.environ.get("LCM_JPEG_ENCODER", "").lower() == "pil"
 
 
 def _encode(rgb: np.ndarray, out_format: str, quality: int) -> bytes:
@@ -64,11 +71,20 @@ class HipSuperResWorker:
             raise RuntimeError("HipSuperResWorker is closed")
         return self.net.upscale_rgb(rgb, magnitude)
 
+    def upscale_jpeg(self, rgb: np.ndarray, magnitude: int = 1, quality: int = 92) -> bytes:
+        if self.net is None:
+            raise RuntimeError("HipSuperResWorker is closed")
+        return self.net.upscale_jpeg(rgb, magnitude, quality)
+
     def upscale_once(self, image_bytes: bytes, out_format: str = "png", quality: int = 92) -> bytes:
         fmt = _check_format(out_format)
+        if fmt == "jpeg" and not _pil_jpeg():
+            return self.upscale_jpeg(_decode(image_bytes), 1, quality)
         return _encode(self.upscale_rgb(_decode(image_bytes), 1), fmt, quality)
 
     def upscale_bytes(self, image_bytes: bytes, *, magnitude: int, out_format: str, quality: int) -> bytes:
         mag = _sr.check_magnitude(magnitude)
         fmt = _check_format(out_format)
+        if fmt == "jpeg" and not _pil_jpeg():
+            return self.upscale_jpeg(_decode(image_bytes), mag, quality)
         return _encode(self.upscale_rgb(_decode(image_bytes), mag), fmt, quality)

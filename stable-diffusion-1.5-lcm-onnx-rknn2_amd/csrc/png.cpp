@@ -407,17 +407,20 @@ void encode_stripe(Stripe& st) {
 }
 
 // ------------------------------------------------------------------------------------------------ worker threads
-// A handful of detached threads, started on first use; a call hands them its stripes and works on them itself as well.
+// A handful of detached threads, started on first use; a call hands them its items (PNG stripes here, restart intervals in
+// jpeg.cpp) and works on them itself as well.
 class Pool {
   public:
+    typedef void (*Task)(void* ctx, size_t i);
     explicit Pool(int n) {
         for (int i = 0; i < n; ++i) std::thread([this] { run(); }).detach();
     }
-    void for_each(std::vector<Stripe>& items) {
+    // fn(ctx, i) for every i < n, on the pool's threads and the caller's
+    void for_each(size_t n, Task fn, void* ctx) {
         struct Batch { size_t next = 0, done = 0; } b;
         {
             std::lock_guard<std::mutex> g(m_);
-            owners_.push_back({&b.next, &b.done, &items});
+            owners_.push_back({&b.next, &b.done, n, fn, ctx});
         }
         cv_.notify_all();
         // the caller takes items too (no idle wait, and progress is guaranteed whatever the pool is busy with)
@@ -425,33 +428,34 @@ class Pool {
             size_t i;
             {
                 std::lock_guard<std::mutex> g(m_);
-                if (b.next >= items.size()) break;
+                if (b.next >= n) break;
                 i = b.next++;
             }
-            encode_stripe(items[i]);
+            fn(ctx, i);
             std::lock_guard<std::mutex> g(m_);
             b.done++;
         }
         std::unique_lock<std::mutex> g(m_);
-        done_cv_.wait(g, [&] { return b.done == items.size(); });
+        done_cv_.wait(g, [&] { return b.done == n; });
         for (size_t k = 0; k < owners_.size(); ++k)
             if (owners_[k].next == &b.next) { owners_.erase(owners_.begin() + k); break; }
     }
 
   private:
-    struct Owner { size_t* next; size_t* done; std::vector<Stripe>* items; };
+    struct Owner { size_t* next; size_t* done; size_t n; Task fn; void* ctx; };
     void run() {
         std::unique_lock<std::mutex> g(m_);
         for (;;) {
             Owner* o = nullptr;
             for (auto& c : owners_)
-                if (*c.next < c.items->size()) { o = &c; break; }
+                if (*c.next < c.n) { o = &c; break; }
             if (!o) { cv_.wait(g); continue; }
             const size_t i = (*o->next)++;
-            std::vector<Stripe>* items = o->items;
+            const Task fn = o->fn;
+            void* const ctx = o->ctx;
             size_t* done = o->done;
             g.unlock();
-            encode_stripe((*items)[i]);
+            fn(ctx, i);
             g.lock();
             (*done)++;
             done_cv_.notify_all();
@@ -476,7 +480,12 @@ Pool* pool() {
 
 inline void put_be32(uint8_t* p, uint32_t v) { p[0] = v >> 24; p[1] = v >> 16; p[2] = v >> 8; p[3] = v; }
 
+void encode_stripe_task(void* ctx, size_t i) { encode_stripe((*(std::vector<Stripe>*)ctx)[i]); }
+
 }  // namespace
+
+// The library's one pool of host threads, shared with the JPEG entropy coder (jpeg.cpp): fn(ctx, i) for every i < n.
+void lcm_host_pool_for_each(size_t n, void (*fn)(void* ctx, size_t i), void* ctx) { pool()->for_each(n, fn, ctx); }
 
 // Upper bound of the file size for lcm_png_encode_rgb8 (stored blocks + framing).
 extern "C" long long lcm_png_bound(int width, int height, int stripes) {
@@ -514,7 +523,7 @@ extern "C" int lcm_png_encode_rgb8(const void* rgb, int width, int height, long 
     }
     if ((long long)(8 + 25 + 10 + off + 8 + 12) > out_cap) { lcm_set_error("png_encode: internal bound error"); return LCM_EINVAL; }
     if (stripes == 1) encode_stripe(st[0]);
-    else pool()->for_each(st);
+    else pool()->for_each(st.size(), encode_stripe_task, &st);
 
     uint8_t* o = (uint8_t*)out;
     static const uint8_t SIG[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n'};

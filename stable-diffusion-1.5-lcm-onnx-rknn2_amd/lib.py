@@ -96,8 +96,12 @@ _SIGS = {
     "lcm_sr_conv4_shuffle": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp],
     "lcm_sr_chroma_h": [_vp, _i, _i, _i, _vp, _vp],
     "lcm_sr_merge": [_vp, _vp, _i, _i, _i, _vp, _vp],
+    "lcm_jpeg_quant_tables": [_i, _vp],
+    "lcm_jpeg_dct_rgb8": [_vp, _i, _i, C.c_longlong, _i, _vp, C.c_longlong, _vp],
+    "lcm_jpeg_encode_coefs": [_vp, _i, _i, _i, _i, _vp, C.c_longlong, C.POINTER(C.c_longlong)],
 }
-EXPORTS = tuple(sorted(list(_SIGS) + ["lcm_last_error", "lcm_version", "lcm_groupnorm_ws_bytes", "lcm_stats_bytes", "lcm_png_bound"]))
+EXPORTS = tuple(sorted(list(_SIGS) + ["lcm_last_error", "lcm_version", "lcm_groupnorm_ws_bytes", "lcm_stats_bytes", "lcm_png_bound",
+                              "lcm_jpeg_coef_bytes", "lcm_jpeg_bound"]))
 
 _lib = None
 
@@ -127,6 +131,9 @@ def load():
     lib.lcm_png_bound.restype = C.c_longlong
     lib.lcm_png_bound.argtypes = [_i, _i, _i]
     lib.lcm_stats_bytes.argtypes = [_i, _i, _i]
+    for fn in (lib.lcm_jpeg_coef_bytes, lib.lcm_jpeg_bound):
+        fn.restype = C.c_longlong
+        fn.argtypes = [_i, _i]
     _install_plans(lib)
     _lib = lib
     return lib

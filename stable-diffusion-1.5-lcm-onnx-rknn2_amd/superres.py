@@ -9,7 +9,9 @@ bicubic and merges -- all on the device (csrc/sr.hip).  Deliberate deviations fr
   * an image side shorter than the tile is run at its own size (the network is fully convolutional; the NPU model's fixed
     224x224 input cannot take such an image at all), e.g. the 64x64 previews;
   * between the passes of ``magnitude`` > 1 the image stays on the device as uint8 RGB.  For PNG this is the reference's lossless
-    round trip; for JPEG only the final image is encoded (the reference re-encodes every pass, losing quality each time).
+    round trip; for JPEG only the final image is encoded (the reference re-encodes every pass, losing quality each time);
+  * JPEG output is written by the library (``JpegEncoder``: csrc/jpeg.hip + csrc/jpeg.cpp), not by PIL: same tables, sampling
+    and Huffman tables as PIL's default, a float DCT and one restart interval per MCU row, so the bytes differ from PIL's.
 """
 from __future__ import annotations
 
@@ -42,6 +44,18 @@ def check_magnitude(magnitude) -> int:
     if mag < 1 or mag > 3:
         raise RuntimeError("magnitude must be 1..3")                                      # lcm_sr_server.py:400-401
     return mag
+
+
+def check_quality(quality) -> int:
+    q = int(quality)
+    if q < 1 or q > 100:
+        raise RuntimeError("quality must be 1..100")
+    return q
+
+
+def jpeg_threads() -> int:
+    """Restart intervals coded at a time (csrc/jpeg.cpp).  The file's bytes do not depend on it."""
+    return max(1, int(os.environ.get("LCM_JPEG_THREADS", "8")))
 
 
 def tile_plan(size: int, tile: int) -> list:
@@ -282,6 +296,48 @@ def _ptr(t) -> int:
     return t.data_ptr()
 
 
+class JpegEncoder:
+    """Device RGB8 -> baseline 4:2:0 JPEG file bytes: ``lcm_jpeg_dct_rgb8`` (csrc/jpeg.hip) on the caller's stream, the
+    coefficients into a pinned host buffer, ``lcm_jpeg_encode_coefs`` (csrc/jpeg.cpp) on the host.  The pixels never cross to
+    the host.  The pinned buffer and the output buffer are kept between calls (they grow to the largest image seen), so an
+    instance serves one thread at a time."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.L = _lib.load()
+        self._pinned = None
+        self._out = None
+
+    def encode_device(self, rgb, quality: int, stream) -> bytes:
+        """rgb: uint8 [H][W][3] device tensor whose rows are dense (any row pitch), produced on ``stream``."""
+        import ctypes
+        q = check_quality(quality)
+        if rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[2] != 3 or rgb.stride(2) != 1 or rgb.stride(1) != 3:
+            raise ValueError(f"JPEG encoder expects a uint8 [H][W][3] device tensor with dense rows, got {tuple(rgb.shape)} "
+                             f"{rgb.dtype} strides {tuple(rgb.stride())}")
+        L = self.L
+        H, W = int(rgb.shape[0]), int(rgb.shape[1])
+        nbytes = int(L.lcm_jpeg_coef_bytes(W, H))
+        if nbytes <= 0:
+            raise RuntimeError(f"JPEG cannot hold a {W}x{H} image (1..65535 a side)")
+        if self._pinned is None or self._pinned.numel() * 2 < nbytes:
+            self._pinned = torch.empty(nbytes // 2, dtype=torch.int16, pin_memory=True)
+        host = self._pinned[:nbytes // 2]
+        with torch.cuda.device(self.device), torch.cuda.stream(stream):
+            coefs = torch.empty(nbytes // 2, dtype=torch.int16, device=self.device)
+            _lib.check(L.lcm_jpeg_dct_rgb8(_ptr(rgb), W, H, int(rgb.stride(0)), q, _ptr(coefs), nbytes, stream.cuda_stream),
+                       "lcm_jpeg_dct_rgb8")
+            host.copy_(coefs, non_blocking=True)
+        stream.synchronize()
+        cap = int(L.lcm_jpeg_bound(W, H))
+        if self._out is None or self._out.size < cap:
+            self._out = np.empty(cap, np.uint8)          # a worst-case bound: only the pages the file touches become real
+        n = ctypes.c_longlong(0)
+        _lib.check(L.lcm_jpeg_encode_coefs(host.data_ptr(), W, H, q, jpeg_threads(), self._out.ctypes.data, self._out.size,
+                                           ctypes.byref(n)), "lcm_jpeg_encode_coefs")
+        return self._out[:n.value].tobytes()
+
+
 class SuperResNet:
     """Device-resident super-resolution-10 (weights packed to fp16 once) and the pass driver.  One instance per worker: it
     owns a stream; a call allocates its workspace on that stream, so instances may run on several threads at once."""
@@ -301,6 +357,7 @@ class SuperResNet:
         with torch.cuda.device(self.device):
             self.stream = torch.cuda.Stream(self.device)
             self.w = {k: v.to(self.device) for k, v in pack_weights(self.sd).items()}
+        self.jpeg = None                 # JpegEncoder, built by the first upscale_jpeg
         self.ws_bytes = int(float(os.environ.get("LCM_SR_WS_MB", "1024")) * (1 << 20)) if ws_mb is None else int(ws_mb * (1 << 20))
 
     def tiles_per_chunk(self, tw: int, th: int) -> int:
@@ -360,6 +417,24 @@ class SuperResNet:
         self.stream.synchronize()
         return host.numpy()
 
+    def upscale_jpeg(self, rgb, magnitude: int = 1, quality: int = 92) -> bytes:
+        """uint8 [H][W][3] host array -> JPEG file bytes of the image after ``magnitude`` passes.  The passes, the JPEG front
+        end (csrc/jpeg.hip) and the copy of its coefficients run on self.stream; the upscaled RGB stays on the device."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"upscale_jpeg expects uint8 [H][W][3], got shape {rgb.shape}")
+        mag = check_magnitude(magnitude)
+        q = check_quality(quality)
+        for k in range(mag):
+            check_pixels(rgb.shape[1] * R ** k, rgb.shape[0] * R ** k)
+        if self.jpeg is None:
+            self.jpeg = JpegEncoder(self.device)
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            src = torch.from_numpy(rgb).to(self.device, non_blocking=False)
+            out = self.upscale_device(src, mag)
+        return self.jpeg.encode_device(out, q, self.stream)
+
     def close(self):
         self.w = {}
         self.sd = {}
+        self.jpeg = None

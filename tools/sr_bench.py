@@ -3,11 +3,19 @@
 super-resolution-10 shapes).
 
   python tools/sr_bench.py [--reps N] [--out FILE.json]
+  python tools/sr_bench.py --jpeg [--reps N] [--trace-dir DIR] [--out FILE.json]      the JPEG output path (below)
+  rocprofv3 --kernel-trace --stats -d DIR -o NAME --output-format csv -- python tools/sr_bench.py --jpeg-launch-only WxH
 
 Per shape: the GPU part of a pass (device events around the launches of upscale_device, input already on the device), the
 per-kernel split (lcm_profile_begin/end events), host PNG decode and encode, whole HipSuperResWorker.upscale_bytes calls, and
 a torch-CPU fp32 restatement of the network (16 threads) for comparison.  Floors for a pass: network FLOPs at the dense-fp16
-MFMA peak and the layer-by-layer activation traffic at HBM bandwidth."""
+MFMA peak and the layer-by-layer activation traffic at HBM bandwidth.
+
+--jpeg, per shape at quality 92: the lcm_jpeg_dct_rgb8 launch on the upscaled image (device events; with --trace-dir also the
+kernel time of a profiler run made by --jpeg-launch-only) against its floor of 3 B/pixel in + 3 B/pixel out at HBM bandwidth,
+the copy of the coefficients to pinned memory, lcm_jpeg_encode_coefs at 1 and 8 threads, and whole upscale_bytes(jpeg) calls
+through the library against the SAME calls with LCM_JPEG_ENCODER=pil, alternating in rounds; the spread of a path is the
+range of its per-round medians."""
 import argparse
 import ctypes as C
 import io
@@ -78,14 +86,148 @@ def time_host(fn, reps):
     return float(np.median(ts))
 
 
+JPEG_SHAPES = (("512->1536", (512, 512)), ("1536->4608", (1536, 1536)), ("640x360->1080p", (640, 360)))
+JPEG_Q = 92
+
+
+def _events(fn, stream, reps, warm=3):
+    for _ in range(warm):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ts = []
+    for _ in range(reps):
+        e0.record(stream)
+        fn()
+        e1.record(stream)
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return ts
+
+
+def _trace_kernel_us(trace_dir, grid):
+    """Median duration (us) of the jpeg kernel dispatches with this grid (work-items x, y) in the kernel-trace CSVs under
+    trace_dir, or None."""
+    import csv
+    import glob
+    ds = []
+    for path in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
+        with open(path) as f:
+            for row in csv.DictReader(f):
+                if "jpeg_dct_rgb8_kernel" not in row.get("Kernel_Name", ""):
+                    continue
+                if (int(row.get("Grid_Size_X", 0)), int(row.get("Grid_Size_Y", 0))) != grid:
+                    continue
+                ds.append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
+    return (round(float(np.median(ds)), 2), len(ds)) if ds else None
+
+
+def jpeg_launch_only(shape, reps):
+    """The launch alone on a seeded image of the given size, for a profiler run (nothing is timed here)."""
+    W, H = (int(v) for v in shape.lower().split("x"))
+    L = lib.load()
+    rgb = torch.from_numpy(ref.test_images()(W, H, 1)).to("cuda:0")
+    n = int(L.lcm_jpeg_coef_bytes(W, H))
+    coefs = torch.empty(n // 2, dtype=torch.int16, device="cuda:0")
+    s = torch.cuda.current_stream().cuda_stream
+    for _ in range(reps + 3):
+        lib.check(L.lcm_jpeg_dct_rgb8(rgb.data_ptr(), W, H, 3 * W, JPEG_Q, coefs.data_ptr(), n, s), "lcm_jpeg_dct_rgb8")
+    torch.cuda.synchronize()
+    print(json.dumps(dict(shape=shape, launches=reps + 3)))
+
+
+def jpeg_main(a):
+    L = lib.load()
+    net = S.SuperResNet("synthetic", "cuda:0", 224, 672)
+    wk = HipSuperResWorker(0, "synthetic", 224, 672)
+    mk = ref.test_images()
+    rows = []
+    from PIL import Image
+    for name, (W, H) in JPEG_SHAPES:
+        rgb = mk(W, H, 1)
+        OW, OH = 3 * W, 3 * H
+        with torch.cuda.stream(net.stream):
+            up = net.upscale_device(torch.from_numpy(rgb).to(net.device), 1)
+            n = int(L.lcm_jpeg_coef_bytes(OW, OH))
+            coefs = torch.empty(n // 2, dtype=torch.int16, device=net.device)
+            host = torch.empty(n // 2, dtype=torch.int16, pin_memory=True)
+            s = net.stream.cuda_stream
+            kern = _events(lambda: lib.check(L.lcm_jpeg_dct_rgb8(up.data_ptr(), OW, OH, 3 * OW, JPEG_Q, coefs.data_ptr(), n, s)),
+                           net.stream, a.reps)
+            d2h = _events(lambda: host.copy_(coefs, non_blocking=True), net.stream, a.reps)
+        net.stream.synchronize()
+        cap = int(L.lcm_jpeg_bound(OW, OH))
+        out = np.empty(cap, np.uint8)
+        ln = C.c_longlong(0)
+        code = {}
+        for thr in (1, 8):
+            fn = lambda: lib.check(L.lcm_jpeg_encode_coefs(host.data_ptr(), OW, OH, JPEG_Q, thr, out.ctypes.data, cap, C.byref(ln)))  # noqa: E731
+            fn()
+            code[thr] = round(time_host(fn, a.reps), 2)
+        png = io.BytesIO()
+        Image.fromarray(rgb).save(png, format="PNG")
+        data = png.getvalue()
+        call = lambda: wk.upscale_bytes(data, magnitude=1, out_format="jpeg", quality=JPEG_Q)  # noqa: E731
+        per = {"hip": [], "pil": []}
+        sizes = {}
+        for rnd in range(3 + 1):                      # round 0 warms both paths up and is dropped
+            for path in ("hip", "pil"):
+                if path == "pil":
+                    os.environ["LCM_JPEG_ENCODER"] = "pil"
+                else:
+                    os.environ.pop("LCM_JPEG_ENCODER", None)
+                ts = []
+                for _ in range(a.reps if rnd else 2):
+                    t = time.perf_counter()
+                    sizes[path] = len(call())
+                    ts.append((time.perf_counter() - t) * 1e3)
+                if rnd:
+                    per[path].append(float(np.median(ts)))
+        os.environ.pop("LCM_JPEG_ENCODER", None)
+        floor_us = (3.0 * OW * OH + n) / PEAK_BW * 1e6
+        k_med = float(np.median(kern)) * 1e3
+        row = dict(shape=name, out_w=OW, out_h=OH, quality=JPEG_Q, reps=a.reps,
+                   kernel_us_events_median=round(k_med, 2), kernel_us_events_min=round(min(kern) * 1e3, 2),
+                   kernel_floor_us_8TBps=round(floor_us, 2), kernel_floor_fraction_events=round(floor_us / k_med, 3),
+                   d2h_ms_median=round(float(np.median(d2h)), 3), coef_bytes=n,
+                   host_coding_ms_1_thread=code[1], host_coding_ms_8_threads=code[8], jpeg_file_bytes=int(ln.value),
+                   upscale_bytes_jpeg_ms=dict(
+                       library_round_medians=[round(v, 2) for v in per["hip"]], pil_round_medians=[round(v, 2) for v in per["pil"]],
+                       library_median=round(float(np.median(per["hip"])), 2), pil_median=round(float(np.median(per["pil"])), 2),
+                       library_spread=round(max(per["hip"]) - min(per["hip"]), 2), pil_spread=round(max(per["pil"]) - min(per["pil"]), 2)),
+                   file_bytes=sizes)
+        if a.trace_dir:
+            grid = (((OW + 15) // 16 + 15) // 16 * 256, (OH + 15) // 16)
+            tr = _trace_kernel_us(a.trace_dir, grid)
+            if tr:
+                row["kernel_us_rocprof_median"], row["kernel_rocprof_dispatches"] = tr
+                row["kernel_floor_fraction_rocprof"] = round(floor_us / tr[0], 3)
+        e = row["upscale_bytes_jpeg_ms"]
+        e["library_faster_by_more_than_spread"] = bool(e["library_median"] + e["library_spread"] + e["pil_spread"] < e["pil_median"])
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    res = dict(device=torch.cuda.get_device_name(0), reps=a.reps, jpeg_threads=S.jpeg_threads(), rows=rows)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+    wk.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out", default="")
+    ap.add_argument("--jpeg", action="store_true", help="measure the JPEG output path instead")
+    ap.add_argument("--jpeg-launch-only", default="", metavar="WxH", help="only launch lcm_jpeg_dct_rgb8 (for a profiler run)")
+    ap.add_argument("--trace-dir", default="", help="with --jpeg: kernel-trace CSVs of --jpeg-launch-only runs")
     ap.add_argument("--cpu-threads", type=int, default=16)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "sr_bench needs the MI355X"
     torch.set_num_threads(a.cpu_threads)
+    if a.jpeg_launch_only:
+        return jpeg_launch_only(a.jpeg_launch_only, a.reps)
+    if a.jpeg:
+        return jpeg_main(a)
     net = S.SuperResNet("synthetic", "cuda:0", 224, 672)
     wk = HipSuperResWorker(0, "synthetic", 224, 672)
     mk = ref.test_images()
