@@ -27,6 +27,7 @@ extern "C" {
 #define LCM_OK 0
 #define LCM_EINVAL (-1)   /* shape / alignment precondition violated */
 #define LCM_ENODEV (-2)   /* no gfx950 device */
+#define LCM_EUNSUPPORTED (-3)   /* a well-formed input of a kind the library leaves to another decoder (JPEG input) */
 
 #define LCM_EPI_NONE 0
 #define LCM_EPI_GEGLU 1   /* out[m][j] = x*gelu(g); weight rows interleaved x/g in blocks of 16 */
@@ -399,6 +400,57 @@ int lcm_jpeg_dct_rgb8(const void* rgb, int W, int H, long long pitch, int qualit
                       void* stream);
 int lcm_jpeg_encode_coefs(const void* coefs, int W, int H, int quality, int threads, void* out, long long out_cap,
                           long long* out_len);
+
+/* ---- JPEG file -> RGB8 on the device (the ``Image.open(io.BytesIO(image_bytes)).convert("RGB")`` of the super-resolution
+ * worker): a host marker parser and entropy decoder, and a device back end.  The pixels equal libjpeg-turbo's default decode
+ * (PIL's) byte for byte.
+ *   Supported: baseline and extended sequential Huffman (SOF0, SOF1), 8 bit, ONE interleaved scan, Y only (sampling 1x1) or
+ *     Y Cb Cr with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1 (4:4:4, 4:2:2, 4:2:0), any DHT tables, with or without DRI;
+ *     APPn / COM are skipped.  Everything else -- progressive, lossless, arithmetic coding, 12 bit, 4 components, 3 components
+ *     that are not YCbCr (an Adobe marker whose transform is not 1; ids other than 1 2 3 without a JFIF marker), other sampling
+ *     factors, several scans or a marker other than RSTn / EOI after the scan, 16-bit DQT, a height given by DNL -- returns
+ *     LCM_EUNSUPPORTED: the caller gives the file to another decoder.  Malformed input is LCM_EINVAL.
+ *   dec_info (host): fills lcm_jpeg_info from the markers; nothing is decoded.
+ *   dec_coefs (host, no GPU work): Huffman-decodes the scan into
+ *       coefs int16 [mcus_y][mcus_x][blocks_per_mcu][64]
+ *     blocks in the order of the file (the luma blocks of the MCU row by row, then Cb, then Cr), every block in ZIGZAG order as
+ *     stored -- for 4:2:0 exactly the layout of lcm_jpeg_dct_rgb8 / lcm_jpeg_encode_coefs, [my][mx][6][64] Y00 Y01 Y10 Y11 Cb Cr.
+ *     An MCU is 8 hmax x 8 vmax pixels; grayscale is one block per MCU.  With a restart interval the intervals are found by
+ *     scanning for FFD0..FFD7 and decoded `threads` at a time on the pool the PNG writer owns, DC prediction starting from 0 in
+ *     each: the result does not depend on `threads`.  Without DRI the scan is one interval on one thread.  A bad code, a run
+ *     past the end of a block, a missing / surplus / out-of-sequence RSTn, an interval that ends early or leaves a byte or more
+ *     unread, no EOI, a DC value outside +-2047 or an AC value outside +-1023 are LCM_EINVAL.
+ *   idct_rgb8 (device, two launches on `stream`, capturable; nothing is allocated or synchronised): coefs of that layout (16-byte
+ *     aligned, coefs_bytes >= info->coefs_bytes) -> H rows of W RGB8 pixels `pitch` bytes apart at rgb_out (any alignment); only
+ *     those 3 W bytes of a row are written.  work: 16-byte aligned device scratch of info->work_bytes (the sample planes between
+ *     the launches).  Of info it reads width, height, ncomp, sampling and qt.  Arithmetic, all integer:
+ *       dequantise: coefficient x table entry.  Inverse DCT: the "slow integer" 8x8 transform (Loeffler-Ligtenberg-Moschytz,
+ *       13-bit constants FIX(x) = round(x * 8192): 0.298631336 0.390180644 0.541196100 0.765366865 0.899976223 1.175875602
+ *       1.501321110 1.847759065 1.961570560 2.053119869 2.562915447 3.072711026), columns first with the result
+ *       (x + 2^10) >> 11 (PASS1_BITS = 2 extra bits kept), then rows with (x + 2^17) >> 18, in 32-bit two's complement that
+ *       wraps (it cannot for coefficients of 8-bit samples), arithmetic shifts; + 128; clamp to 0..255.
+ *       Chroma of a 2x2 file ("fancy" upsampling; C = the component's own ceil(W/2) x ceil(H/2) samples, indices clamped to
+ *       them): v[r][c] = 3 C[r >> 1][c] + C[(r >> 1) -+ 1][c] (- for even r, + for odd r); out[r][2c] = (3 v[r][c] + v[r][c-1] +
+ *       8) >> 4, out[r][2c+1] = (3 v[r][c] + v[r][c+1] + 7) >> 4.  Of a 2x1 file: out[2c] = (3 C[c] + C[c-1] + 1) >> 2,
+ *       out[2c+1] = (3 C[c] + C[c+1] + 2) >> 2, except that the first and the last output column are C[0] and C[last].  A
+ *       component of one or two samples' width is replicated instead (out[r][x] = C[r >> 1][x >> 1], resp. C[r][x >> 1]).
+ *       Colour, with b = Cb - 128, r = Cr - 128:  R = Y + ((91881 r + 32768) >> 16),  G = Y + ((-22554 b - 46802 r + 32768) >> 16),
+ *       B = Y + ((116130 b + 32768) >> 16), clamped.  Grayscale: R = G = B = Y. */
+typedef struct lcm_jpeg_info {
+    int width, height;
+    int ncomp;                 /* 1 (Y) or 3 (Y Cb Cr) */
+    int sampling;              /* luma sampling: 0 = 1x1 (4:4:4 and grayscale), 1 = 2x1 (4:2:2), 2 = 2x2 (4:2:0) */
+    int restart_interval;      /* MCUs per restart interval, 0 = none */
+    int mcus_x, mcus_y;
+    int blocks_per_mcu;        /* 1, 3, 4 or 6 */
+    long long coefs_bytes;     /* mcus_y * mcus_x * blocks_per_mcu * 128 */
+    long long work_bytes;      /* mcus_y * mcus_x * blocks_per_mcu * 64 */
+    uint8_t qt[3][64];         /* quantisation table of every component, natural (row-major) order */
+} lcm_jpeg_info;
+int lcm_jpeg_dec_info(const void* data, long long len, lcm_jpeg_info* info);
+int lcm_jpeg_dec_coefs(const void* data, long long len, int threads, void* coefs, long long coefs_bytes);
+int lcm_jpeg_idct_rgb8(const void* coefs, long long coefs_bytes, const lcm_jpeg_info* info, void* work, long long work_bytes,
+                       void* rgb_out, long long pitch, void* stream);
 
 /* ---- hipGraph capture of the 4-step sampler loop + VAE ---- */
 int lcm_graph_begin(void* stream);

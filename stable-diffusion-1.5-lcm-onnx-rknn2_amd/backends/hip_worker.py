@@ -172,6 +172,40 @@ def encode_jpeg(rgb, quality: int = 92) -> bytes:
         return enc.encode_device(src, q, stream)
 
 
+_JPEG_DECODERS = {}
+
+
+def decode_jpeg(data) -> np.ndarray:
+    """JPEG file bytes -> uint8 [H,W,3] host pixels, equal to ``np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))``: the
+    markers and the entropy decoding on LCM_JPEG_THREADS host threads (csrc/jpeg_dec.cpp), the inverse DCT, chroma upsampling
+    and colour conversion on the current device (csrc/jpeg_dec.hip).  Files the library does not decode (progressive, CMYK,
+    ... -- include/lcm_hip.h), corrupt ones, and everything under LCM_JPEG_DECODER=pil go to PIL.  Callers that want the pixels
+    on the device use ``superres.JpegDecoder`` directly.  One decoder per device, one call at a time."""
+    from .. import superres as _sr
+
+    def pil():
+        from PIL import Image
+        return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+    mode = _sr.jpeg_decoder_mode()
+    if mode == "pil" or bytes(data[:2]) != b"\xff\xd8":
+        return pil()
+    if not torch.cuda.is_available():
+        raise LcmHipError("decode_jpeg needs an MI355X; no CPU fallback exists on this path (LCM_JPEG_DECODER=pil uses PIL)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    with _JPEG_LOCK:
+        dec = _JPEG_DECODERS.get(dev)
+        if dec is None:
+            dec = _JPEG_DECODERS[dev] = _sr.JpegDecoder(dev)
+        stream = torch.cuda.current_stream(dev)
+        out = dec.decode_device(data, stream, 0, mode)
+        if out is not None:
+            with torch.cuda.device(dev), torch.cuda.stream(stream):
+                host = out.cpu()
+            stream.synchronize()
+            return host.numpy()
+    return pil()
+
+
 class _Engine:
     """Everything resident for one (family, device, checkpoint): the pipeline (weights, launch plans, captured graphs), the
     text encoders, the style adapters and the micro-batching dispatcher.  The reference builds one pipeline -- and one

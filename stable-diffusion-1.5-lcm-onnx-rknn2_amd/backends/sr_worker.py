@@ -1,7 +1,9 @@
 """``HipSuperResWorker`` -- the MI355X drop-in for the reference's RKNNLite ``SuperResWorker``
 (server/lcm_sr_server.py:312-405): same constructor and ``upscale_once`` / ``upscale_bytes`` / ``close`` methods, with the tiled
 numpy + NPU loop replaced by the HIP passes of ``superres.SuperResNet`` (csrc/sr.hip).  ``png`` output is written by
-csrc/png.cpp; ``jpeg`` output by csrc/jpeg.hip + csrc/jpeg.cpp from the image on the device (LCM_JPEG_ENCODER=pil: by PIL).  ``SuperResService`` builds
+csrc/png.cpp; ``jpeg`` output by csrc/jpeg.hip + csrc/jpeg.cpp from the image on the device (LCM_JPEG_ENCODER=pil: by PIL).  A JPEG
+*input* is decoded by csrc/jpeg_dec.cpp + csrc/jpeg_dec.hip straight into the device tensor the first pass reads
+(LCM_JPEG_DECODER=pil, and every file the library does not support: by PIL, as every other format).  ``SuperResService`` builds
 SR_NUM_WORKERS of these, each driven from its own thread: every worker has its own stream and workspace.  Install with
 ``server.lcm_sr_server.SuperResWorker = HipSuperResWorker``.  No CPU fallback: without a GPU the constructor
 raises."""
@@ -77,14 +79,26 @@ class HipSuperResWorker:
         return self.net.upscale_jpeg(rgb, magnitude, quality)
 
     def upscale_once(self, image_bytes: bytes, out_format: str = "png", quality: int = 92) -> bytes:
-        fmt = _check_format(out_format)
-        if fmt == "jpeg" and not _pil_jpeg():
-            return self.upscale_jpeg(_decode(image_bytes), 1, quality)
-        return _encode(self.upscale_rgb(_decode(image_bytes), 1), fmt, quality)
+        return self._upscale(image_bytes, 1, _check_format(out_format), quality)
 
     def upscale_bytes(self, image_bytes: bytes, *, magnitude: int, out_format: str, quality: int) -> bytes:
         mag = _sr.check_magnitude(magnitude)
-        fmt = _check_format(out_format)
-        if fmt == "jpeg" and not _pil_jpeg():
-            return self.upscale_jpeg(_decode(image_bytes), mag, quality)
-        return _encode(self.upscale_rgb(_decode(image_bytes), mag), fmt, quality)
+        return self._upscale(image_bytes, mag, _check_format(out_format), quality)
+
+    def _upscale(self, image_bytes: bytes, mag: int, fmt: str, quality: int) -> bytes:
+        lib_jpeg = fmt == "jpeg" and not _pil_jpeg()
+        dev = None
+        if self.net is not None:
+            try:
+                dev = self.net.decode_jpeg(image_bytes, mag)     # None: not a JPEG the library decodes -> PIL
+            except RuntimeError:
+                if lib_jpeg:
+                    _sr.check_quality(quality)                   # a bad quality is reported before a size that is too large
+                raise
+        if dev is None:                                          # the path every input took before, in its order of checks
+            if lib_jpeg:
+                return self.upscale_jpeg(_decode(image_bytes), mag, quality)
+            return _encode(self.upscale_rgb(_decode(image_bytes), mag), fmt, quality)
+        if lib_jpeg:
+            return self.net.upscale_device_jpeg(dev, mag, quality)
+        return _encode(self.net.upscale_device_rgb(dev, mag), fmt, quality)

@@ -99,9 +99,22 @@ _SIGS = {
     "lcm_jpeg_quant_tables": [_i, _vp],
     "lcm_jpeg_dct_rgb8": [_vp, _i, _i, C.c_longlong, _i, _vp, C.c_longlong, _vp],
     "lcm_jpeg_encode_coefs": [_vp, _i, _i, _i, _i, _vp, C.c_longlong, C.POINTER(C.c_longlong)],
+    "lcm_jpeg_dec_info": [_vp, C.c_longlong, _vp],
+    "lcm_jpeg_dec_coefs": [_vp, C.c_longlong, _i, _vp, C.c_longlong],
+    "lcm_jpeg_idct_rgb8": [_vp, C.c_longlong, _vp, _vp, C.c_longlong, _vp, C.c_longlong, _vp],
 }
 EXPORTS = tuple(sorted(list(_SIGS) + ["lcm_last_error", "lcm_version", "lcm_groupnorm_ws_bytes", "lcm_stats_bytes", "lcm_png_bound",
                               "lcm_jpeg_coef_bytes", "lcm_jpeg_bound"]))
+
+EUNSUPPORTED = -3          # LCM_EUNSUPPORTED: a well-formed input the library leaves to another decoder
+
+
+class JpegInfo(C.Structure):
+    """lcm_jpeg_info (include/lcm_hip.h)."""
+    _fields_ = [("width", _i), ("height", _i), ("ncomp", _i), ("sampling", _i), ("restart_interval", _i), ("mcus_x", _i),
+                ("mcus_y", _i), ("blocks_per_mcu", _i), ("coefs_bytes", C.c_longlong), ("work_bytes", C.c_longlong),
+                ("qt", C.c_uint8 * 192)]
+
 
 _lib = None
 

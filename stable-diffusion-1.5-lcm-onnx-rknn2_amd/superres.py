@@ -58,6 +58,19 @@ def jpeg_threads() -> int:
     return max(1, int(os.environ.get("LCM_JPEG_THREADS", "8")))
 
 
+# Which JPEG inputs the library decodes when LCM_JPEG_DECODER is not set: "hip" = every supported file, "dri" = only files
+# with restart markers (their entropy decoding runs on LCM_JPEG_THREADS threads), "pil" = none.  "pil" until the gate of
+# DESIGN.md section 7 ("JPEG input") has been measured on an MI355X: no such measurement exists yet.
+JPEG_DECODER_DEFAULT = "pil"
+
+
+def jpeg_decoder_mode() -> str:
+    """LCM_JPEG_DECODER: "pil" (PIL decodes every input, as before the library had a decoder), "hip", "dri"; anything else,
+    or unset, is JPEG_DECODER_DEFAULT."""
+    m = os.environ.get("LCM_JPEG_DECODER", "").lower()
+    return m if m in ("pil", "hip", "dri") else JPEG_DECODER_DEFAULT
+
+
 def tile_plan(size: int, tile: int) -> list:
     """Tile starts along one axis (lcm_sr_server.py _plan_tiles): 0, t, 2t, ... while a whole tile fits, then size - t.
     ``tile`` is the tile side actually used: min(input_size, size)."""
@@ -338,6 +351,63 @@ class JpegEncoder:
         return self._out[:n.value].tobytes()
 
 
+class JpegDecoder:
+    """JPEG file bytes -> uint8 [H][W][3] device tensor: ``lcm_jpeg_dec_info`` / ``lcm_jpeg_dec_coefs`` (csrc/jpeg_dec.cpp) on the
+    host into a pinned buffer, the copy of the coefficients and ``lcm_jpeg_idct_rgb8`` (csrc/jpeg_dec.hip) on the caller's
+    stream.  The pixels are PIL's ``Image.open(...).convert("RGB")`` byte for byte and never exist on the host.  The pinned
+    buffer is kept between calls (it grows to the largest image seen), so an instance serves one thread at a time."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.L = _lib.load()
+        self._pinned = None
+        self._copied = None              # event after the last copy out of the pinned buffer
+
+    def header(self, data):
+        """-> lib.JpegInfo, or None for anything the library does not decode (progressive, CMYK, ...; not a JPEG at all)."""
+        import ctypes
+        info = _lib.JpegInfo()
+        rc = self.L.lcm_jpeg_dec_info(data, len(data), ctypes.byref(info))
+        return info if rc == 0 else None
+
+    def decode_device(self, data, stream, magnitude: int = 0, mode: str = "hip"):
+        """None = unsupported or corrupt: the caller decodes with PIL (every file PIL read before is still read, and what it
+        refused is still refused by it).  With ``magnitude`` >= 1, SR_MAX_PIXELS is checked for every pass from the header,
+        before anything is decoded.  ``mode`` "dri": files without restart markers are left to the caller as well."""
+        import ctypes
+        data = bytes(data)
+        info = self.header(data)
+        if info is None or (mode == "dri" and info.restart_interval == 0):
+            return None
+        W, H = int(info.width), int(info.height)
+        from PIL import Image
+        if Image.MAX_IMAGE_PIXELS is not None and W * H > Image.MAX_IMAGE_PIXELS:
+            return None                  # PIL warns about, or refuses, an image of this size: that stays PIL's business
+        limit = max_pixels()
+        for k in range(int(magnitude)):
+            check_pixels(W * R ** k, H * R ** k, limit)
+        L = self.L
+        nbytes = int(info.coefs_bytes)
+        if self._copied is not None:
+            self._copied.synchronize()   # the previous call's copy has left the pinned buffer
+        if self._pinned is None or self._pinned.numel() * 2 < nbytes:
+            self._pinned = torch.empty(nbytes // 2, dtype=torch.int16, pin_memory=True)
+        host = self._pinned[:nbytes // 2]
+        if L.lcm_jpeg_dec_coefs(data, len(data), jpeg_threads(), host.data_ptr(), nbytes) != 0:
+            return None
+        with torch.cuda.device(self.device), torch.cuda.stream(stream):
+            coefs = torch.empty(nbytes // 2, dtype=torch.int16, device=self.device)
+            coefs.copy_(host, non_blocking=True)
+            if self._copied is None:
+                self._copied = torch.cuda.Event()
+            self._copied.record(stream)
+            work = torch.empty(int(info.work_bytes), dtype=torch.uint8, device=self.device)
+            out = torch.empty(H, W, 3, dtype=torch.uint8, device=self.device)
+            _lib.check(L.lcm_jpeg_idct_rgb8(_ptr(coefs), nbytes, ctypes.byref(info), _ptr(work), int(info.work_bytes), _ptr(out),
+                                            3 * W, stream.cuda_stream), "lcm_jpeg_idct_rgb8")
+        return out
+
+
 class SuperResNet:
     """Device-resident super-resolution-10 (weights packed to fp16 once) and the pass driver.  One instance per worker: it
     owns a stream; a call allocates its workspace on that stream, so instances may run on several threads at once."""
@@ -358,6 +428,7 @@ class SuperResNet:
             self.stream = torch.cuda.Stream(self.device)
             self.w = {k: v.to(self.device) for k, v in pack_weights(self.sd).items()}
         self.jpeg = None                 # JpegEncoder, built by the first upscale_jpeg
+        self.jpeg_dec = None             # JpegDecoder, built by the first decode_jpeg
         self.ws_bytes = int(float(os.environ.get("LCM_SR_WS_MB", "1024")) * (1 << 20)) if ws_mb is None else int(ws_mb * (1 << 20))
 
     def tiles_per_chunk(self, tw: int, th: int) -> int:
@@ -434,7 +505,37 @@ class SuperResNet:
             out = self.upscale_device(src, mag)
         return self.jpeg.encode_device(out, q, self.stream)
 
+    def decode_jpeg(self, data, magnitude: int = 1):
+        """JPEG file bytes -> uint8 [H][W][3] device tensor on self.stream (csrc/jpeg_dec.cpp + csrc/jpeg_dec.hip), or None when
+        the bytes are not a JPEG the library decodes or LCM_JPEG_DECODER leaves them to PIL.  SR_MAX_PIXELS is checked for
+        ``magnitude`` passes from the header before any decoding."""
+        mode = jpeg_decoder_mode()
+        if mode == "pil" or bytes(data[:2]) != b"\xff\xd8":
+            return None
+        mag = check_magnitude(magnitude)
+        if self.jpeg_dec is None:
+            self.jpeg_dec = JpegDecoder(self.device)
+        return self.jpeg_dec.decode_device(data, self.stream, mag, mode)
+
+    def upscale_device_rgb(self, src, magnitude: int = 1) -> np.ndarray:
+        """upscale_rgb for an image that is already on the device (produced on self.stream): -> host array."""
+        mag = check_magnitude(magnitude)
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            host = self.upscale_device(src, mag).cpu()
+        self.stream.synchronize()
+        return host.numpy()
+
+    def upscale_device_jpeg(self, src, magnitude: int = 1, quality: int = 92) -> bytes:
+        """upscale_jpeg for an image that is already on the device (produced on self.stream): no pixel crosses to the host."""
+        mag = check_magnitude(magnitude)
+        q = check_quality(quality)
+        if self.jpeg is None:
+            self.jpeg = JpegEncoder(self.device)
+        out = self.upscale_device(src, mag)
+        return self.jpeg.encode_device(out, q, self.stream)
+
     def close(self):
         self.w = {}
         self.sd = {}
         self.jpeg = None
+        self.jpeg_dec = None

@@ -15,7 +15,13 @@ MFMA peak and the layer-by-layer activation traffic at HBM bandwidth.
 kernel time of a profiler run made by --jpeg-launch-only) against its floor of 3 B/pixel in + 3 B/pixel out at HBM bandwidth,
 the copy of the coefficients to pinned memory, lcm_jpeg_encode_coefs at 1 and 8 threads, and whole upscale_bytes(jpeg) calls
 through the library against the SAME calls with LCM_JPEG_ENCODER=pil, alternating in rounds; the spread of a path is the
-range of its per-round medians."""
+range of its per-round medians.
+
+--jpeg-in, per input size at quality 92, 4:2:0, with and without a restart marker per MCU row: PIL decode + upload against
+lcm_jpeg_dec_info + lcm_jpeg_dec_coefs (1 and 8 threads) + the copy of the coefficients + lcm_jpeg_idct_rgb8 (device events;
+floor: 2 B per coefficient in + 3 B per pixel out at HBM bandwidth), and whole upscale_bytes(jpeg in, jpeg out) calls with
+LCM_JPEG_DECODER=hip against the SAME calls with LCM_JPEG_DECODER=pil, alternating in rounds as above.
+  rocprofv3 --kernel-trace --stats -d DIR -o NAME --output-format csv -- python tools/sr_bench.py --jpeg-in-launch-only WxH"""
 import argparse
 import ctypes as C
 import io
@@ -213,19 +219,148 @@ def jpeg_main(a):
     wk.close()
 
 
+JPEG_IN_SHAPES = (("512x512", (512, 512)), ("1536x1536", (1536, 1536)), ("4608x3072", (4608, 3072)))
+
+
+def _jpeg_in_file(W, H, dri):
+    from PIL import Image
+    buf = io.BytesIO()
+    kw = dict(restart_marker_rows=1) if dri else {}
+    Image.fromarray(ref.test_images()(W, H, 1)).save(buf, format="JPEG", quality=JPEG_Q, subsampling=2, **kw)
+    return buf.getvalue()
+
+
+def _host_decode(L, data, threads, pinned=None):
+    info = lib.JpegInfo()
+    lib.check(L.lcm_jpeg_dec_info(data, len(data), C.byref(info)), "lcm_jpeg_dec_info")
+    if pinned is None:
+        pinned = torch.empty(info.coefs_bytes // 2, dtype=torch.int16, pin_memory=True)
+    lib.check(L.lcm_jpeg_dec_coefs(data, len(data), threads, pinned.data_ptr(), info.coefs_bytes), "lcm_jpeg_dec_coefs")
+    return info, pinned
+
+
+def jpeg_in_launch_only(shape, reps):
+    """The two launches of lcm_jpeg_idct_rgb8 alone on a seeded 4:2:0 file of the given size, for a profiler run."""
+    W, H = (int(v) for v in shape.lower().split("x"))
+    L = lib.load()
+    info, pinned = _host_decode(L, _jpeg_in_file(W, H, True), 8)
+    coefs = pinned.to("cuda:0")
+    work = torch.empty(info.work_bytes, dtype=torch.uint8, device="cuda:0")
+    out = torch.empty(H, W, 3, dtype=torch.uint8, device="cuda:0")
+    s = torch.cuda.current_stream().cuda_stream
+    for _ in range(reps + 3):
+        lib.check(L.lcm_jpeg_idct_rgb8(coefs.data_ptr(), info.coefs_bytes, C.byref(info), work.data_ptr(), info.work_bytes,
+                                       out.data_ptr(), 3 * W, s), "lcm_jpeg_idct_rgb8")
+    torch.cuda.synchronize()
+    print(json.dumps(dict(shape=shape, launches=reps + 3)))
+
+
+def jpeg_in_main(a):
+    from PIL import Image
+    L = lib.load()
+    wk = HipSuperResWorker(0, "synthetic", 224, 672)
+    stream = torch.cuda.current_stream()
+    rows = []
+    for name, (W, H) in JPEG_IN_SHAPES:
+        for dri in (True, False):
+            data = _jpeg_in_file(W, H, dri)
+            pil = lambda: torch.from_numpy(np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))).to("cuda:0")  # noqa: E731
+            pil()
+            pil_ms = time_host(lambda: (pil(), torch.cuda.synchronize()), a.reps)
+            info, pinned = _host_decode(L, data, 8)
+            hdr = lib.JpegInfo()
+            hdr_ms = time_host(lambda: L.lcm_jpeg_dec_info(data, len(data), C.byref(hdr)), a.reps)
+            ent = {thr: round(time_host(lambda: _host_decode(L, data, thr, pinned), a.reps), 3) for thr in (1, 2, 4, 8, 16)}
+            coefs = torch.empty(info.coefs_bytes // 2, dtype=torch.int16, device="cuda:0")
+            work = torch.empty(info.work_bytes, dtype=torch.uint8, device="cuda:0")
+            out = torch.empty(H, W, 3, dtype=torch.uint8, device="cuda:0")
+            s = stream.cuda_stream
+            h2d = _events(lambda: coefs.copy_(pinned, non_blocking=True), stream, a.reps)
+            kern = _events(lambda: lib.check(L.lcm_jpeg_idct_rgb8(coefs.data_ptr(), info.coefs_bytes, C.byref(info), work.data_ptr(),
+                                                                  info.work_bytes, out.data_ptr(), 3 * W, s)), stream, a.reps)
+            assert np.array_equal(out.cpu().numpy(), np.asarray(Image.open(io.BytesIO(data)).convert("RGB")))
+            call = lambda: wk.upscale_bytes(data, magnitude=1, out_format="jpeg", quality=JPEG_Q)  # noqa: E731
+            per = {"hip": [], "pil": []}
+            shas = {}
+            for rnd in range(3 + 1):                  # round 0 warms both paths up and is dropped
+                for path in ("hip", "pil"):
+                    os.environ["LCM_JPEG_DECODER"] = path
+                    ts = []
+                    for _ in range(a.reps if rnd else 2):
+                        t = time.perf_counter()
+                        res = call()
+                        ts.append((time.perf_counter() - t) * 1e3)
+                    shas[path] = hash(res)
+                    if rnd:
+                        per[path].append(float(np.median(ts)))
+            os.environ.pop("LCM_JPEG_DECODER", None)
+            assert shas["hip"] == shas["pil"]
+            floor_us = (info.coefs_bytes + 3.0 * W * H) / PEAK_BW * 1e6
+            k_med = float(np.median(kern)) * 1e3
+            e = dict(library_round_medians=[round(v, 2) for v in per["hip"]], pil_round_medians=[round(v, 2) for v in per["pil"]],
+                     library_median=round(float(np.median(per["hip"])), 2), pil_median=round(float(np.median(per["pil"])), 2),
+                     library_spread=round(max(per["hip"]) - min(per["hip"]), 2), pil_spread=round(max(per["pil"]) - min(per["pil"]), 2))
+            e["library_faster_by_more_than_spread"] = bool(e["library_median"] + e["library_spread"] + e["pil_spread"] < e["pil_median"])
+            row = dict(shape=name, W=W, H=H, quality=JPEG_Q, sampling="4:2:0", restart_markers=dri, file_bytes=len(data), reps=a.reps,
+                       pil_decode_plus_upload_ms=round(pil_ms, 3), header_ms=round(hdr_ms, 4), entropy_decode_ms_by_threads=ent,
+                       coef_bytes=int(info.coefs_bytes), h2d_ms_median=round(float(np.median(h2d)), 3),
+                       kernels_us_events_median=round(k_med, 2), kernels_us_events_min=round(min(kern) * 1e3, 2),
+                       kernels_floor_us_8TBps=round(floor_us, 2), kernels_floor_fraction_events=round(floor_us / k_med, 3),
+                       upscale_bytes_jpeg_in_jpeg_out_ms=e)
+            if a.trace_dir:
+                tr = _trace_dec_us(a.trace_dir, W, H)
+                if tr:
+                    row.update(tr)
+                    row["kernels_floor_fraction_rocprof"] = round(floor_us / tr["kernels_us_rocprof_median_sum"], 3)
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+    res = dict(device=torch.cuda.get_device_name(0), reps=a.reps, jpeg_threads=S.jpeg_threads(), rows=rows)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+    wk.close()
+
+
+def _trace_dec_us(trace_dir, W, H):
+    """Median durations (us) of the two decoder kernels for a W x H 4:2:0 image in the kernel-trace CSVs under trace_dir."""
+    import csv
+    import glob
+    nblocks = ((W + 15) // 16) * ((H + 15) // 16) * 6
+    grids = {"jpeg_idct_kernel": ((nblocks + 31) // 32 * 256, 1), "jpeg_upsample_rgb_kernel": ((((W + 3) // 4 + 255) // 256) * 256, H)}
+    ds = {k: [] for k in grids}
+    for path in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
+        with open(path) as f:
+            for row in csv.DictReader(f):
+                for k, g in grids.items():
+                    if k in row.get("Kernel_Name", "") and (int(row.get("Grid_Size_X", 0)), int(row.get("Grid_Size_Y", 0))) == g:
+                        ds[k].append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
+    if not all(ds.values()):
+        return None
+    med = {k: round(float(np.median(v)), 2) for k, v in ds.items()}
+    return dict(kernels_us_rocprof_median=med, kernels_us_rocprof_median_sum=round(sum(med.values()), 2),
+                kernels_rocprof_dispatches={k: len(v) for k, v in ds.items()})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out", default="")
     ap.add_argument("--jpeg", action="store_true", help="measure the JPEG output path instead")
     ap.add_argument("--jpeg-launch-only", default="", metavar="WxH", help="only launch lcm_jpeg_dct_rgb8 (for a profiler run)")
-    ap.add_argument("--trace-dir", default="", help="with --jpeg: kernel-trace CSVs of --jpeg-launch-only runs")
+    ap.add_argument("--jpeg-in", action="store_true", help="measure the JPEG input path instead")
+    ap.add_argument("--jpeg-in-launch-only", default="", metavar="WxH", help="only launch lcm_jpeg_idct_rgb8 (for a profiler run)")
+    ap.add_argument("--trace-dir", default="", help="with --jpeg / --jpeg-in: kernel-trace CSVs of the launch-only runs")
     ap.add_argument("--cpu-threads", type=int, default=16)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "sr_bench needs the MI355X"
     torch.set_num_threads(a.cpu_threads)
     if a.jpeg_launch_only:
         return jpeg_launch_only(a.jpeg_launch_only, a.reps)
+    if a.jpeg_in_launch_only:
+        return jpeg_in_launch_only(a.jpeg_in_launch_only, a.reps)
+    if a.jpeg_in:
+        return jpeg_in_main(a)
     if a.jpeg:
         return jpeg_main(a)
     net = S.SuperResNet("synthetic", "cuda:0", 224, 672)
