@@ -314,6 +314,20 @@ int lcm_scheduler_step(const void* eps, const void* eps_uncond, float guidance, 
 int lcm_scheduler_step_ex(const void* eps, const void* eps_uncond, float guidance, void* lat, const void* noise,
                           const float* coef6, int last, int prediction_type, int B, int h, int w, void* stream);
 
+/* ---- multi-pass refinement in latent space ----
+ * lat_out = fmaf(sqrt_b, noise, sqrt_a * x0) over fp32 NCHW [B,4,h,w] in one launch (16-byte accesses: every pointer 16-byte
+ * aligned).  dup != 0: lat_out is [2B,4,h,w] and both halves (the two classifier-free-guidance rows of each request) get the
+ * value.  Starts a chain from denoised latents of an earlier pass. */
+int lcm_latents_renoise(const void* x0, const void* noise, float sqrt_a, float sqrt_b, void* lat_out, int B, int h, int w,
+                        int dup, void* stream);
+/* The last step of a pass that another pass follows, as one launch: den as lcm_scheduler_step_ex(last = 1) forms it (bit-equal),
+ * stored to xk (fp32 NCHW [B,4,h,w]); lat <- fmaf(next_sqrt_b, noise, next_sqrt_a * den), the next pass's first state -- the
+ * same bits lcm_latents_renoise gives for (xk, noise).  dup != 0: lat points at the second half of a [2B,4,h,w] state (as the
+ * CFG call of lcm_scheduler_step_ex does) and the first half receives the same values.  coef6[4..5] are unused. */
+int lcm_scheduler_step_handover(const void* eps, const void* eps_uncond, float guidance, void* lat, const void* noise, void* xk,
+                                const float* coef6, float next_sqrt_a, float next_sqrt_b, int prediction_type, int B, int h, int w,
+                                int dup, void* stream);
+
 /* ---- adaptive_avg_pool2d(lat,(8,8)) -> fp16 [B,4,8,8] (run_job_with_latents, backends/cuda_worker.py:299-304) */
 int lcm_latents_pool8(const void* lat, void* out_f16, int B, int h, int w, void* stream);
 

@@ -12,6 +12,8 @@ Env (as the reference, backends/cuda_worker.py:43-61):
   LCM_PREDICTION_TYPE        epsilon | v_prediction | sample: overrides the prediction type guessed for a single-file
                              checkpoint (weights.single_file_prediction_type; e.g. epsilon for SD 2.x-base)
   CUDA_DEVICE / HIP_DEVICE   default cuda:0 (torch's name for the HIP device)
+  LCM_REFINE_CACHE_MB        device-resident cache of refinement latents (denoise_strength / pass_number requests), MB per
+                             engine; default 64, 0 turns it off
   CUDA_DTYPE                 fp16 (default).  bf16 / fp32 -- which the reference honours -- are REFUSED unless LCM_HIP_DTYPE=fp16
                              says to run them in this backend's one arithmetic (fp16 operands, fp32 accumulation)
 """
@@ -33,6 +35,7 @@ from ..pipeline import LcmHipPipeline
 from ..prompt import HipPromptEncoder
 from ..scheduler import LCMSchedule
 from .. import weights as _weights
+from . import refine as _refine
 
 
 def parse_size(size) -> Tuple[int, int]:
@@ -240,6 +243,11 @@ class _Engine:
         self.lane_encoders = {}      # lane -> per-lane views of the text encoders
         self._style_cv = threading.Condition()
         self._style_users = 0        # passes currently running with `active_style` merged into the shared weights
+        # refinement requests (denoise_strength / pass_number): the denoised latents x^k of every pass they run stay on the
+        # device so that pass p of a request starts from its pass p - 1.  Plain requests never touch it.
+        self.refine_cache = _refine.RefineCache(_refine.cache_bytes_from_env())
+        self._stats_lock = threading.Lock()
+        self.stats = dict(unet_evals=0, refine_cache_hits=0, refine_cache_misses=0, refine_cache_puts=0)
 
     # ---- style LoRAs (backends/cuda_worker.py:123-196) -----------------------------------------
     def _want_style(self, style_id, level):
@@ -299,7 +307,7 @@ class _Engine:
     def run_batch(self, key, items, lane=0):
         """One batched sampler pass for ``items`` = [(req, seed[, noise])], all of ``key``, on lane ``lane``;
         -> per-item (rgb, pool8 row)."""
-        width, height, steps, g, style_id, level = key
+        width, height, steps, g, style_id, level = key[:6]
         import time as _t
         t0 = _t.perf_counter()
         lane = lane % self.n_lanes
@@ -315,13 +323,65 @@ class _Engine:
                     pe, kw = self.family_cls._conditioning(self, reqs, width, height, g, lane)
                 t1 = _t.perf_counter()
                 noises = [it[2] for it in items] if all(len(it) > 2 and it[2] is not None for it in items) else None
-                out = pipe.generate(pe, [it[1] for it in items], width, height, steps, g, noises=noises, lane=lane, **kw)
+                if len(key) > 6:
+                    res = self._run_refine(pipe, key, items, noises, pe, kw, lane, stream)
+                else:
+                    out = pipe.generate(pe, [it[1] for it in items], width, height, steps, g, noises=noises, lane=lane, **kw)
+                    res = [(out["rgb"][i], out["pool8"][i:i + 1]) for i in range(len(items))]
+                    with self._stats_lock:
+                        self.stats["unet_evals"] += steps
             finally:
                 self._leave_style()
         t2 = _t.perf_counter()
         if self.timing is not None:                  # LCM_WORKER_TIMING=1: (batch, conditioning s, sampler call s, end time)
             self.timing.append((len(items), t1 - t0, t2 - t1, t2))
-        return [(out["rgb"][i], out["pool8"][i:i + 1]) for i in range(len(items))]
+        return res
+
+    def _run_refine(self, pipe, key, items, noises, pe, kw, lane, stream):
+        """The passes of a refinement batch (key = plain key + (d, p)).  Every item starts from its deepest cached x^k, k < p;
+        items of one sampler pass must share that depth, so the batch is split by it (and each part cut to the plan batch
+        sizes).  Every x^k a pass produces goes into the cache.  The bytes never depend on where a chain started: the draws of
+        the passes left out are skipped, and the re-noise launch gives the bits of the hand-over step."""
+        width, height, steps, g = key[:4]
+        d, p = key[6], key[7]
+        cache = self.refine_cache
+        idents = [_refine.request_ident(it[0], key, it[1]) for it in items]
+        found = [cache.deepest(idn, d, p) if cache.cap > 0 else (None, None) for idn in idents]
+        res = [None] * len(items)
+
+        def rows(x, idx):                            # per-request conditioning rows of a sub-batch
+            if isinstance(x, torch.Tensor) and x.dim() > 0 and x.shape[0] == len(items):
+                return x[idx]
+            if isinstance(x, tuple):
+                return tuple(rows(y, idx) for y in x)
+            return x
+        for k0, idx in _refine.group_by_start([f[0] for f in found], self.batch_sizes):
+            whole = len(idx) == len(items)
+            with torch.cuda.stream(stream):          # the rows are gathered on the lane's stream, behind the text encoder
+                sub_pe = pe if whole else pe[idx]
+                sub_kw = kw if whole else {n: rows(v, idx) for n, v in kw.items()}
+            start = None if k0 is None else (k0, [found[i][1] for i in idx])
+            out = pipe.generate(sub_pe, [items[i][1] for i in idx], width, height, steps, g,
+                                noises=[noises[i] for i in idx] if noises is not None else None, lane=lane,
+                                strength=d, passes=p, start=start, **sub_kw)
+            puts = 0
+            if cache.cap > 0:
+                first = out["xk_first"]
+                with torch.cuda.stream(stream):
+                    for j in range(0 if k0 is None else 1, out["xk"].shape[0]):
+                        for b, i in enumerate(idx):
+                            ck = idents[i] + (d, first + j)
+                            if ck not in cache:      # a repeated (padding) item, or a depth another lane just filled
+                                puts += bool(cache.put(ck, out["xk"][j, b].clone()))
+                stream.synchronize()                 # the copies have landed before another lane may read them
+            with self._stats_lock:
+                self.stats["unet_evals"] += out["unet_evals"]
+                self.stats["refine_cache_hits"] += len(idx) if k0 is not None else 0
+                self.stats["refine_cache_misses"] += len(idx) if k0 is None else 0
+                self.stats["refine_cache_puts"] += puts
+            for b, i in enumerate(idx):
+                res[i] = (out["rgb"][b], out["pool8"][b:b + 1])
+        return res
 
     def start_batcher(self):
         mb = int(os.environ.get("LCM_MICROBATCH", "8") or 0)
@@ -363,6 +423,7 @@ class _Engine:
                 pipe.close()                          # graphs dropped, split-K workspaces unregistered
             self.encode, self.enc, self.tok, self.styles, self.active_style = None, [], [], {}, None
             self.lane_encoders = {}
+            self.refine_cache.clear()
         finally:
             for lk in self.lane_locks:
                 lk.release()
@@ -564,14 +625,18 @@ class HipLcmWorker:
     # ------------------------------------------------------------------------------------------
     @staticmethod
     def _job_key(req):
-        """What must agree for jobs to share one batched pass: geometry, step count, guidance and style merge."""
+        """What must agree for jobs to share one batched pass: geometry, step count, guidance and style merge -- and, for a
+        refinement request (``denoise_strength`` / ``pass_number``, backends/refine.py), its strength and pass number: those
+        get a key of their own (the plain fields plus (d, p)) and never share a pass with plain requests."""
         width, height = parse_size(req.size)
         sl = getattr(req, "style_lora", None)
         style_id = getattr(sl, "style", None) if sl else None
         level = int(getattr(sl, "level", 0) or 0) if sl else 0
         if not style_id or level <= 0:
             style_id, level = None, 0
-        return (width, height, int(req.num_inference_steps), float(req.guidance_scale), style_id, level)
+        key = (width, height, int(req.num_inference_steps), float(req.guidance_scale), style_id, level)
+        rf = _refine.parse_refine(req)
+        return key if rf is None else key + rf
 
     def _run_batch(self, key, items):
         return self._engine.run_batch(key, items)
@@ -584,8 +649,15 @@ class HipLcmWorker:
         # thread: pool threads do it in parallel and the GPU dispatcher's serial path shrinks by ~0.5 ms per request
         from ..pipeline import draw_noise
         noise = None
+        n_draws = key[2]
+        if len(key) > 6:                             # refinement: the schedule's own error first, then the whole chain's draws
+            try:
+                eng.pipe.sched.timesteps(key[2], key[6])
+            except ValueError as e:
+                raise RuntimeError(str(e))
+            n_draws = _refine.noise_draws(key[2], key[7])
         if key[0] % 8 == 0 and key[1] % 8 == 0 and key[0] > 0 and key[1] > 0 and key[2] >= 1:
-            noise = draw_noise(seed, key[1] // 8, key[0] // 8, key[2] - 1, eng.pipe.sched.init_noise_sigma)
+            noise = draw_noise(seed, key[1] // 8, key[0] // 8, n_draws - 1, eng.pipe.sched.init_noise_sigma)
         return (req, seed, noise)
 
     def _submit(self, job):

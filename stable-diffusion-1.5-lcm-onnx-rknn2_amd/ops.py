@@ -445,6 +445,28 @@ def scheduler_step(eps, lat, noise, coef6, last, B, h, w, *, eps_uncond=None, gu
     return lat
 
 
+def latents_renoise(x0, noise, sqrt_a, sqrt_b, lat, B, h, w, *, dup=False):
+    """lat <- sqrt_a x0 + sqrt_b noise (fp32 NCHW); dup: ``lat`` is [2B,4,h,w] and both halves are written."""
+    L = _lib.load()
+    _lib.check(L.lcm_latents_renoise(_p(x0), _p(noise), float(sqrt_a), float(sqrt_b), _p(lat), B, h, w, int(bool(dup)), _stream()),
+               "lcm_latents_renoise")
+    return lat
+
+
+def scheduler_step_handover(eps, lat, noise, xk, coef6, next_sqrt_a, next_sqrt_b, B, h, w, *, eps_uncond=None, guidance=1.0,
+                            pred="epsilon", dup=False):
+    """The last step of a refinement pass that another pass follows: xk <- the denoised latents (the bits of the ``last`` step),
+    lat <- them re-noised for the next pass.  dup: ``lat`` is the second half of a [2B,4,h,w] state; the first half is written too."""
+    if pred not in _lib.PREDICTION_TYPES:
+        raise ValueError(f"unknown prediction type {pred!r}: expected one of {sorted(_lib.PREDICTION_TYPES)}")
+    L = _lib.load()
+    arr = (C.c_float * 6)(*[float(c) for c in coef6])
+    rc = L.lcm_scheduler_step_handover(_p(eps), _p(eps_uncond), float(guidance), _p(lat), _p(noise), _p(xk), arr, float(next_sqrt_a),
+                                       float(next_sqrt_b), _lib.PREDICTION_TYPES[pred], B, h, w, int(bool(dup)), _stream())
+    _lib.check(rc, "lcm_scheduler_step_handover")
+    return lat
+
+
 def latents_pool8(lat, out, B, h, w):
     L = _lib.load()
     _lib.check(L.lcm_latents_pool8(_p(lat), _p(out), B, h, w, _stream()), "lcm_latents_pool8")

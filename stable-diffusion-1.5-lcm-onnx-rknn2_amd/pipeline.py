@@ -105,12 +105,14 @@ class _Lane:
 
 
 class _Plan:
-    """Buffers + captured graph for one (B, h, w, steps, cfg) key."""
+    """Buffers + captured graph for one (B, h, w, steps, cfg) key.  refine = (strength, passes to run, starts from cached
+    latents) makes it the plan of a refinement chain (LcmHipPipeline._enqueue_refine); None: the plain sampler."""
 
-    def __init__(self, pipe, B, h, w, steps, do_cfg, lane=None):
+    def __init__(self, pipe, B, h, w, steps, do_cfg, lane=None, refine=None):
         # Every zero-fill below must be ordered before the first use on the lane's (non-blocking) stream: allocate
         # under that stream, or a fill still queued on the null stream can land AFTER the request's uploads.
         self.lane = lane if lane is not None else pipe.lanes[0]
+        self.refine = refine
         with torch.cuda.stream(self.lane.stream):
             self._init(pipe, B, h, w, steps, do_cfg)
 
@@ -125,7 +127,15 @@ class _Plan:
                        if pipe.unet.has_added else None)          # SDXL: [pooled text embeds | sinusoid(time ids)]
         self.lat0 = torch.zeros(B, 4, h, w, dtype=torch.float32, device=dev)         # request input
         self.lat = torch.zeros(UB, 4, h, w, dtype=torch.float32, device=dev)          # sampler state
-        self.noise = torch.zeros(max(steps - 1, 1), B, 4, h, w, dtype=torch.float32, device=dev)
+        # noise tensors of the chain: the plain pass's steps - 1, then `steps` per refinement pass (its re-noise draw first)
+        n_noise = max(steps - 1, 1)
+        self.xk = None
+        if self.refine is not None:
+            _, run, cached = self.refine
+            n_noise = max(run * steps + (0 if cached else steps - 1), 1)
+            # xk[0]: the latents the chain starts from (uploaded from the cache, or the plain pass's x^0); xk[j]: j passes later
+            self.xk = torch.zeros(run + 1, B, 4, h, w, dtype=torch.float32, device=dev)
+        self.noise = torch.zeros(n_noise, B, 4, h, w, dtype=torch.float32, device=dev)
         self.eps = torch.zeros(UB, h, w, 4, dtype=torch.float32, device=dev)
         self.rgb = torch.zeros(B, h * VAE_SCALE_FACTOR, w * VAE_SCALE_FACTOR, 3, dtype=torch.uint8, device=dev)
         self.pool8 = torch.zeros(B, 4, 8, 8, dtype=torch.float16, device=dev)
@@ -134,7 +144,7 @@ class _Plan:
         self.graph = None
         # pinned staging for H2D / D2H
         self.h_lat = torch.zeros(B, 4, h, w, dtype=torch.float32).pin_memory()
-        self.h_noise = torch.zeros(max(steps - 1, 1), B, 4, h, w, dtype=torch.float32).pin_memory()
+        self.h_noise = torch.zeros(n_noise, B, 4, h, w, dtype=torch.float32).pin_memory()
         self.h_rgb = torch.zeros(B, h * VAE_SCALE_FACTOR, w * VAE_SCALE_FACTOR, 3, dtype=torch.uint8).pin_memory()
         self.h_pool8 = torch.zeros(B, 4, 8, 8, dtype=torch.float16).pin_memory()
         self.h_latout = torch.zeros(B, 4, h, w, dtype=torch.float32).pin_memory()
@@ -184,6 +194,8 @@ class LcmHipPipeline:
 
     def _enqueue(self, P: _Plan, guidance: float, want_float=False, taps=None):
         """Enqueue the whole sampler on the current stream (this is what gets captured)."""
+        if P.refine is not None:
+            return self._enqueue_refine(P, guidance, want_float=want_float, taps=taps)
         B, UB, h, w = P.B, P.UB, P.h, P.w
         unet, vae = P.lane.unet, P.lane.vae
         ts = self.sched.timesteps(P.steps)
@@ -217,16 +229,72 @@ class LcmHipPipeline:
         vae.decode(final, B, h, w, P.rgb, img_f32=P.img_f32 if want_float else None, taps=taps)
         return final
 
-    def plan(self, B, h, w, steps, do_cfg=False, guidance=None, lane=0) -> _Plan:
+    def _enqueue_refine(self, P: _Plan, guidance: float, want_float=False, taps=None):
+        """The refinement chain of P.refine = (d, run, cached) as one enqueue (one captured graph): the plain pass that gives x^0
+        (unless the chain starts from cached latents in P.xk[0], re-noised by lcm_latents_renoise), then `run` passes over the
+        strength-cut schedule.  A pass that another one follows ends in the hand-over step (x^k to P.xk, the re-noised state of
+        the next pass to P.lat, one launch); the last pass ends in the plain `last` step and only its x goes through the VAE."""
+        B, UB, h, w = P.B, P.UB, P.h, P.w
+        unet, vae = P.lane.unet, P.lane.vae
+        d, run, cached = P.refine
+        pred = self.sched.prediction_type
+        ts_cut = self.sched.timesteps(P.steps, d)
+        nsa, nsb = self.sched.renoise_coefficients(ts_cut[0])
+        ni = 0                                        # next tensor of P.noise, in draw order
+        if cached:
+            ops.latents_renoise(P.xk[0], P.noise[0], nsa, nsb, P.lat, B, h, w, dup=P.do_cfg)
+            ni = 1
+            passes = [ts_cut] * run
+        else:
+            if P.do_cfg:
+                P.lat[:B].copy_(P.lat0)
+                P.lat[B:].copy_(P.lat0)
+            else:
+                P.lat.copy_(P.lat0)
+            passes = [self.sched.timesteps(P.steps)] + [ts_cut] * run
+        kv = unet.encode_context(P.ehs, UB)
+        aug = unet.encode_added(P.add_in, UB) if unet.has_added else None
+        wemb = P.wemb if unet.has_cond else None
+        state = P.lat[B:] if P.do_cfg else P.lat
+        eps = P.eps[B:] if P.do_cfg else P.eps
+        kw = dict(eps_uncond=P.eps[:B], guidance=guidance) if P.do_cfg else {}
+        ta_all, ta_ts = None, None
+        for j, ts in enumerate(passes):
+            if len(ts) <= unet.MAX_HOISTED_STEPS and (ta_ts is None or list(ta_ts) != list(ts)):
+                ta_all, ta_ts = unet.time_embed_all([int(t) for t in ts], wemb, UB, aug), ts    # once per distinct schedule
+            for i, t in enumerate(ts):
+                unet.forward(P.lat, int(t), kv, wemb, UB, h, w, P.eps, taps=taps if (i == 0 and j == 0) else None, aug=aug,
+                             ta=ta_all[i * UB:(i + 1) * UB] if ta_all is not None else None)
+                coef, last = self.sched.step_coefficients(ts, i)
+                if last and j < len(passes) - 1:
+                    ops.scheduler_step_handover(eps, state, P.noise[ni], P.xk[j + 1 if cached else j], coef, nsa, nsb, B, h, w,
+                                                pred=pred, dup=P.do_cfg, **kw)
+                    ni += 1
+                else:
+                    ops.scheduler_step(eps, state, P.noise[min(ni, P.noise.shape[0] - 1)], coef, last, B, h, w, pred=pred, **kw)
+                    if not last:
+                        ni += 1
+                        if P.do_cfg:
+                            P.lat[:B].copy_(P.lat[B:])
+        P.xk[run].copy_(state)
+        ops.latents_pool8(state, P.pool8, B, h, w)
+        if want_float and P.img_f32 is None:
+            P.img_f32 = torch.zeros(B, h * 8, w * 8, 3, dtype=torch.float32, device=self.device)
+        vae.decode(state, B, h, w, P.rgb, img_f32=P.img_f32 if want_float else None, taps=taps)
+        return state
+
+    def plan(self, B, h, w, steps, do_cfg=False, guidance=None, lane=0, refine=None) -> _Plan:
         # classifier-free guidance bakes the guidance value into the captured step kernels: one plan per value
         key = (B, h, w, steps, do_cfg, round(float(guidance), 4) if do_cfg and guidance is not None else None)
+        if refine is not None:                       # (d, passes to run, starts from cached latents): a chain of its own
+            key = key + (round(float(refine[0]), 6), int(refine[1]), bool(refine[2]))
         L = self.lane(lane)
         P = L.plans.get(key)
         if P is None:
             with self._build_lock:
                 P = L.plans.get(key)
                 if P is None:
-                    P = _Plan(self, B, h, w, steps, do_cfg, L)
+                    P = _Plan(self, B, h, w, steps, do_cfg, L, refine=refine)
                     L.plans[key] = P
         return P
 
@@ -288,12 +356,20 @@ class LcmHipPipeline:
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def generate(self, prompt_embeds, seeds, width, height, steps, guidance_scale=1.0, negative_embeds=None,
-                 want_float=False, taps=None, latents=None, added=None, negative_added=None, noises=None, lane=0):
+                 want_float=False, taps=None, latents=None, added=None, negative_added=None, noises=None, lane=0,
+                 strength=None, passes=0, start=None):
         """prompt_embeds: [B,77,ctx] (any float dtype, host or device); seeds: B ints.  noises: optional per-request
         ``draw_noise(seed, h, w, steps - 1, init_noise_sigma)`` results drawn ahead by the callers (the worker's pool
         threads draw them in parallel, off the dispatcher's serial path); None: drawn here from the seeds.
         lane: which of the pipeline's concurrent sampler instances runs the request (calls on different lanes may overlap;
         calls on one lane must be serialised by the caller).
+        passes > 0: refinement in latent space -- the plain request's final latents x^0, then ``passes`` times: re-noise to
+        the first timestep of ``timesteps(steps, strength)`` and run the LCM steps over that schedule; the image is the decode
+        of x^passes.  A request's RNG stream is then ``draw_noise(seed, h, w, steps * (passes + 1) - 1)``: the plain request's
+        tensors first, then per pass its re-noise draw and its steps - 1 step noises.  start = (k, [B device tensors fp32
+        [4,h,w]]): the chain starts from these x^k (0 <= k < passes) and runs passes - k passes; the draws of the passes
+        left out are skipped, so the result does not depend on where the chain started.  The result then carries
+        ``xk_first`` and ``xk`` (device fp32 [n,B,4,h,w]: x^xk_first ... x^passes) and ``unet_evals``.
         Returns dict(rgb uint8 [B,H,W,3] (host), latents fp32 [B,4,h,w] (host), pool8 fp16 [B,4,8,8] (host))."""
         torch.cuda.set_device(self.device)        # the pool may call from a thread other than the constructing one
         pe = torch.as_tensor(prompt_embeds)
@@ -307,7 +383,22 @@ class LcmHipPipeline:
             raise LcmHipError("classifier-free guidance needs negative_embeds")
         if self.unet.has_added and added is None:
             raise LcmHipError("this UNet needs added=(pooled_text_embeds [B,P], time_ids [B,6]) (SDXL text_time embedding)")
-        P = self.plan(B, h, w, steps, do_cfg, guidance_scale, lane=lane)
+        passes = int(passes or 0)
+        refine, n_extra, skip = None, steps - 1, 0
+        if passes > 0:
+            if latents is not None:
+                raise LcmHipError("refinement passes draw their noise from the seeds: latents= is not supported with passes > 0")
+            k0 = int(start[0]) if start is not None else None
+            if k0 is not None and not 0 <= k0 < passes:
+                raise LcmHipError(f"start depth {k0} outside [0, passes={passes})")
+            dd = 1.0 if strength is None else float(strength)
+            self.sched.timesteps(steps, dd)           # diffusers' error for steps > original_steps x strength, before any plan
+            refine = (dd, passes - (k0 or 0), k0 is not None)
+            n_extra = steps * (passes + 1) - 1
+            skip = steps * (k0 + 1) - 1 if k0 is not None else 0
+        elif strength is not None and float(strength) != 1.0:
+            raise LcmHipError("strength needs passes >= 1")
+        P = self.plan(B, h, w, steps, do_cfg, guidance_scale, lane=lane, refine=refine)
         stream = P.lane.stream
         with torch.cuda.stream(stream):
             # ---- host-side request state -> device (outside the graph) ----
@@ -316,12 +407,19 @@ class LcmHipPipeline:
                     P.h_lat[b].copy_(torch.as_tensor(latents[b]).reshape(4, h, w))
                     extra = []
                 else:
-                    l0, extra = noises[b] if noises is not None else draw_noise(s, h, w, steps - 1, self.sched.init_noise_sigma)
+                    l0, extra = noises[b] if noises is not None else draw_noise(s, h, w, n_extra, self.sched.init_noise_sigma)
+                    if refine is not None:
+                        if len(extra) != n_extra:
+                            raise LcmHipError(f"request {b}: {len(extra)} noise tensors drawn ahead, the chain needs {n_extra}")
+                        extra = extra[skip:]
                     P.h_lat[b].copy_(l0[0])
                 for i, n in enumerate(extra):
                     P.h_noise[i, b].copy_(n[0])
             P.lat0.copy_(P.h_lat, non_blocking=True)
             P.noise.copy_(P.h_noise, non_blocking=True)
+            if refine is not None and refine[2]:
+                for b in range(B):
+                    P.xk[0, b].copy_(start[1][b].reshape(4, h, w), non_blocking=True)
             pe16 = pe.to(torch.float16).reshape(B * TEXT_SEQ_LEN, -1)
             if do_cfg:
                 ne16 = torch.as_tensor(negative_embeds).to(torch.float16).reshape(B * TEXT_SEQ_LEN, -1)
@@ -367,8 +465,12 @@ class LcmHipPipeline:
             P.h_rgb.copy_(P.rgb, non_blocking=True)
             P.h_pool8.copy_(P.pool8, non_blocking=True)
             P.h_latout.copy_(final, non_blocking=True)
+            xk = P.xk.clone() if refine is not None else None
             stream.synchronize()
         out = dict(rgb=P.h_rgb.numpy().copy(), latents=P.h_latout.numpy().copy(), pool8=P.h_pool8.numpy().copy())
+        if refine is not None:
+            out["xk"], out["xk_first"] = xk, passes - refine[1]
+            out["unet_evals"] = steps * (refine[1] + (0 if refine[2] else 1))
         if want_float:
             out["image"] = P.img_f32.cpu().numpy()   # NHWC float, pre-clamp
         return out

@@ -47,15 +47,31 @@ class LCMSchedule:
                 "timestep_scaling", "sigma_data", "set_alpha_to_one", "prediction_type")
         return cls(**{k: cfg[k] for k in keys if k in cfg})
 
-    def timesteps(self, n: int) -> np.ndarray:
+    def timesteps(self, n: int, strength: float = 1.0) -> np.ndarray:
+        """``LCMScheduler.set_timesteps(n, strength=strength)``: the LCM training schedule cut to its last
+        ``int(original_inference_steps * strength)`` timesteps, ``n`` of them taken at even spacing.  strength 1.0 is the
+        text-to-image schedule."""
         if n < 1:
             raise ValueError("num_inference_steps must be >= 1")
         k = self.num_train_timesteps // self.original_inference_steps
-        origin = (np.arange(1, self.original_inference_steps + 1) * k - 1)[::-1].copy()
-        if n > len(origin):
-            raise ValueError(f"num_inference_steps={n} exceeds original_inference_steps={len(origin)}")
+        if strength == 1.0:
+            origin = (np.arange(1, self.original_inference_steps + 1) * k - 1)[::-1].copy()
+            if n > len(origin):
+                raise ValueError(f"num_inference_steps={n} exceeds original_inference_steps={len(origin)}")
+        else:
+            m = int(self.original_inference_steps * float(strength))
+            origin = (np.arange(1, m + 1) * k - 1)[::-1].copy()
+            if n > m:
+                raise ValueError(f"The combined original_steps x strength: {m} is smaller than num_inference_steps: {n}. Make sure "
+                                 f"to either reduce num_inference_steps to a value smaller than {m} or increase strength to a "
+                                 f"value higher than {float(n) / self.original_inference_steps}.")
         idx = np.floor(np.linspace(0, len(origin), num=n, endpoint=False)).astype(np.int64)
         return origin[idx].astype(np.int64)
+
+    def renoise_coefficients(self, t: int):
+        """-> (sqrt(alphas_cumprod[t]), sqrt(1 - alphas_cumprod[t])): ``add_noise`` at timestep t (a refinement pass's start)."""
+        a_t = float(self.alphas_cumprod[int(t)])
+        return a_t ** 0.5, (1 - a_t) ** 0.5
 
     def step_coefficients(self, ts: np.ndarray, i: int):
         """-> ([sqrt_a_t, sqrt_b_t, c_skip, c_out, sqrt_a_prev, sqrt_b_prev], last)."""
