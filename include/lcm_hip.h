@@ -204,6 +204,23 @@ int lcm_set_conv_impl(int impl);
 int lcm_conv3x3_c4_f32in(const void* in, const void* pre_w, const void* pre_b, float in_scale,
                          const void* W, const void* bias, void* out, int B, int H, int Wd, int Cout, void* stream);
 
+/* The same with a residual: out = conv(in) + bias + res, res fp16 [B,H,W,Cout] added in fp32 before the one fp16 rounding
+ * (ControlNet: conv_in(latents) + hint embedding).  No pre-transform. */
+int lcm_conv3x3_c4_res_f32in(const void* in, const void* W, const void* bias, const void* res, void* out, int B, int H,
+                             int Wd, int Cout, void* stream);
+
+/* ---- ControlNet hint stack (ControlNetConditioningEmbedding): narrow 3x3 convolutions, csrc/controlnet.hip ----
+ * lcm_hint_conv_u8: in uint8 RGB [B,H,W,3], x / 255 applied in the kernel and carried as fp16 hi + lo (~22 bits);
+ *   W fp16 [Cout][9][3]; out fp16 [B,H,W,Cout]; Cout % 16 == 0.
+ * lcm_hint_conv_f16: in fp16 [B,H,W,Cin], Cin in {16, 32, 96}; W fp16 [Cout][9][Cin]; out fp16 [B,Ho,Wo,Cout];
+ *   stride 1 or 2 (padding 1: Ho = ceil(H / 2)); Cout % 16 == 0.
+ * Both: fp32 accumulation in one chain per output (no K split: a pixel's bits depend on its own inputs only),
+ * bias then optional SiLU in fp32, one fp16 rounding.  Any H, W >= 1. */
+int lcm_hint_conv_u8(const void* in, const void* W, const void* bias, void* out, int B, int H, int Wd, int Cout, int silu,
+                     void* stream);
+int lcm_hint_conv_f16(const void* in, const void* W, const void* bias, void* out, int B, int H, int Wd, int Cin, int Cout,
+                      int stride, int silu, void* stream);
+
 /* ---- 3x3 convolution to a few channels (UNet conv_out -> eps; VAE decoder.conv_out -> RGB) ----
  * in: fp16 [B,H,W,Cin], W: fp16 [Cout][9][Cin], Cout <= 4, Cin % 8 == 0.
  * mode 0: out fp32 [B,H,W,Cout];  mode 1: out u8 [B,H,W,Cout] = rint(clamp(y/2+0.5,0,1)*255)

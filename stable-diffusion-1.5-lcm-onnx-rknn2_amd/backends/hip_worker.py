@@ -35,6 +35,7 @@ from ..pipeline import LcmHipPipeline
 from ..prompt import HipPromptEncoder
 from ..scheduler import LCMSchedule
 from .. import weights as _weights
+from . import controlnet as _controlnet
 from . import refine as _refine
 
 
@@ -247,7 +248,29 @@ class _Engine:
         # device so that pass p of a request starts from its pass p - 1.  Plain requests never touch it.
         self.refine_cache = _refine.RefineCache(_refine.cache_bytes_from_env())
         self._stats_lock = threading.Lock()
-        self.stats = dict(unet_evals=0, refine_cache_hits=0, refine_cache_misses=0, refine_cache_puts=0)
+        self.stats = dict(unet_evals=0, refine_cache_hits=0, refine_cache_misses=0, refine_cache_puts=0, controlnet_evals=0)
+        # ControlNet: where it comes from (CONTROLNET=<dir or file> | "synthetic" | None); loaded on the first request that
+        # carries a hint, released with the pipeline
+        self.controlnet_src = None
+        self.synthetic_model = False
+        self._controlnet_lock = threading.Lock()
+
+    def ensure_controlnet(self):
+        """Load the ControlNet on first use.  RuntimeError when none is configured, when this family has none (SDXL) or when it
+        does not fit the UNet."""
+        pipe = self.pipe
+        if pipe is None:
+            raise RuntimeError("worker engine is closed")
+        if not self.family_cls.CONTROLNET_OK:
+            raise RuntimeError("controlnet_image: SDXL ControlNets are not supported by this worker (SD1.5 and SD 2.x only)")
+        if pipe.controlnet is not None:
+            return
+        if not self.controlnet_src:
+            raise RuntimeError("controlnet_image was sent but no ControlNet is loaded (set CONTROLNET=<dir or .safetensors file>)")
+        with self._controlnet_lock:
+            if pipe.controlnet is None:
+                sd, cfg = _controlnet.load_controlnet_source(self.controlnet_src, pipe.unet.cfg, self.synthetic_model)
+                pipe.set_controlnet(sd, cfg)
 
     # ---- style LoRAs (backends/cuda_worker.py:123-196) -----------------------------------------
     def _want_style(self, style_id, level):
@@ -323,7 +346,15 @@ class _Engine:
                     pe, kw = self.family_cls._conditioning(self, reqs, width, height, g, lane)
                 t1 = _t.perf_counter()
                 noises = [it[2] for it in items] if all(len(it) > 2 and it[2] is not None for it in items) else None
-                if len(key) > 6:
+                if _controlnet.is_control_key(key):
+                    hints = np.stack([it[3] for it in items])
+                    out = pipe.generate(pe, [it[1] for it in items], width, height, steps, g, noises=noises, lane=lane,
+                                        control=(hints, key[7]), **kw)
+                    res = [(out["rgb"][i], out["pool8"][i:i + 1]) for i in range(len(items))]
+                    with self._stats_lock:
+                        self.stats["unet_evals"] += steps
+                        self.stats["controlnet_evals"] += steps
+                elif len(key) > 6:
                     res = self._run_refine(pipe, key, items, noises, pe, kw, lane, stream)
                 else:
                     out = pipe.generate(pe, [it[1] for it in items], width, height, steps, g, noises=noises, lane=lane, **kw)
@@ -437,9 +468,13 @@ class HipLcmWorker:
     """SD1.5-family worker (drop-in for DiffusersCudaWorker, backends/cuda_worker.py:20-304)."""
 
     FAMILY = "sd15"
+    CONTROLNET_OK = True
 
-    def __init__(self, worker_id: int):
+    def __init__(self, worker_id: int, controlnet: str = None):
+        """controlnet: a diffusers ControlNet directory or .safetensors file ("synthetic" with MODEL=synthetic*); None: the
+        CONTROLNET environment variable.  Loaded on the first request that carries ``controlnet_image``."""
         self.worker_id = worker_id
+        cn_src = (controlnet if controlnet is not None else os.environ.get("CONTROLNET") or "").strip() or None
         self._engine = None
         model_root = (os.environ.get("MODEL_ROOT") or "").strip()
         model_name = (os.environ.get("MODEL") or "").strip()
@@ -469,7 +504,7 @@ class HipLcmWorker:
         # synthetic weights: the engine is keyed by the synthetic model's name (synthetic / synthetic-sd2 differ)
         synth_name = model_name if model_name.startswith("synthetic") else "synthetic"
         ekey = (self.FAMILY, device, synth_name if synthetic else os.path.join(model_root, model_name),
-                tuple(sorted((sid, sd.path()) for sid, sd in STYLE_REGISTRY.items())))
+                tuple(sorted((sid, sd.path()) for sid, sd in STYLE_REGISTRY.items())), cn_src)
         with _ENGINES_LOCK:
             ref = _ENGINES.get(ekey) if share else None
             eng = ref() if ref is not None else None
@@ -527,6 +562,7 @@ class HipLcmWorker:
         with torch.cuda.stream(eng.pipe.stream):
             self._load_text_encoders(eng, device, ckpt_root, clip_sd, text_cfg)
         eng.refs = 1
+        eng.controlnet_src, eng.synthetic_model = cn_src, bool(synthetic)
         self._engine = eng
         self._load_styles(eng)
         eng.start_batcher()
@@ -636,6 +672,12 @@ class HipLcmWorker:
             style_id, level = None, 0
         key = (width, height, int(req.num_inference_steps), float(req.guidance_scale), style_id, level)
         rf = _refine.parse_refine(req)
+        ctl = _controlnet.parse_control(req)
+        if ctl is not None:
+            # ControlNet jobs coalesce among themselves: the plain key + the conditioning scale (the hint is per image)
+            if rf is not None:
+                raise RuntimeError("controlnet_image is not combined with refinement (denoise_strength < 1 or pass_number > 1)")
+            return key + (_controlnet.KEY_TAG, ctl[0])
         return key if rf is None else key + rf
 
     def _run_batch(self, key, items):
@@ -650,6 +692,13 @@ class HipLcmWorker:
         from ..pipeline import draw_noise
         noise = None
         n_draws = key[2]
+        if _controlnet.is_control_key(key):
+            eng.ensure_controlnet()                  # lazily, on the caller's thread; raises for this job
+            hint = _controlnet.fit_hint(_controlnet.parse_control(req)[1], key[0], key[1])
+            noise = None
+            if key[0] % 8 == 0 and key[1] % 8 == 0 and key[0] > 0 and key[1] > 0 and key[2] >= 1:
+                noise = draw_noise(seed, key[1] // 8, key[0] // 8, n_draws - 1, eng.pipe.sched.init_noise_sigma)
+            return (req, seed, noise, hint)
         if len(key) > 6:                             # refinement: the schedule's own error first, then the whole chain's draws
             try:
                 eng.pipe.sched.timesteps(key[2], key[6])
@@ -881,6 +930,7 @@ class HipLcmWorker:
 
 
 class HipLcmSDXLWorker(HipLcmWorker):
+    CONTROLNET_OK = False        # a hint sent here raises for its job (SDXL ControlNets are out of scope)
     """SDXL worker (drop-in for DiffusersSDXLCudaWorker, backends/cuda_worker.py:307-614): two text encoders
     (CLIP-L hidden_states[-2] | OpenCLIP-bigG hidden_states[-2] -> 2048; pooled bigG text_embeds), size/crop time ids,
     classifier-free guidance when guidance_scale > 1 (negative conditioning = zeros, force_zeros_for_empty_prompt)."""

@@ -82,10 +82,14 @@ def set_pool_queue(q, worker=None) -> None:
 def create_hip_worker(worker_id: int):
     kind = detect_worker_type()
     from .hip_worker import HipLcmSDXLWorker, HipLcmWorker
+    # CONTROLNET=<diffusers ControlNet directory | .safetensors file | "synthetic" with MODEL=synthetic*>: loaded by the worker on
+    # the first request that carries controlnet_image (backends/controlnet.py)
+    cn = (os.environ.get("CONTROLNET") or "").strip()
+    kw = dict(controlnet=cn) if cn else {}
     if kind == "sdxl":
-        w = HipLcmSDXLWorker(worker_id=worker_id)                    # backends/worker_factory.py:93
+        w = HipLcmSDXLWorker(worker_id=worker_id, **kw)              # backends/worker_factory.py:93
     else:
-        w = HipLcmWorker(worker_id=worker_id)                        # backends/worker_factory.py:97
+        w = HipLcmWorker(worker_id=worker_id, **kw)                  # backends/worker_factory.py:97
     q = _POOL_QUEUE() if _POOL_QUEUE is not None else None
     if q is not None:
         w.bind_queue(q)

@@ -206,30 +206,31 @@ class _Net:
 
 
 # ==================================================================================================
-class UNetHip(_Net):
-    def __init__(self, sd: dict, cfg: dict | None = None, device="cuda"):
-        super().__init__(device)
-        self.cfg = cfg = unet_config(cfg)
+class _UNetEncoder(_Net):
+    """What UNet2DConditionModel and ControlNetModel have in common: conv_in, the time embedding, the down blocks and the mid
+    block -- their packers and their launches.  UNetHip adds the up blocks, ControlNetHip the hint stack and the zero convolutions."""
+
+    def _init_encoder(self, cfg):
+        self.cfg = cfg
         boc = cfg["block_out_channels"]
         self.ctx_dim = cfg["cross_attention_dim"]
         self.temb_dim = boc[0] * 4
-        nb = len(boc)
-        temb_list, kv_list = [], []
         self.qs = {}                                                     # per transformer block: the factor carried by its to_q rows
+        self.has_cond = bool(cfg.get("time_cond_proj_dim"))
+        self.has_added = bool(cfg.get("addition_time_embed_dim"))       # SDXL "text_time" embedding
+
+    def _pack_head(self, sd):
         self._put("conv_in.w", pack_conv3x3(sd["conv_in.weight"]))
         self._put("conv_in.b", sd["conv_in.bias"])
         for n in ("linear_1", "linear_2"):
             self._put(f"te.{n}.w", sd[f"time_embedding.{n}.weight"])
             self._put(f"te.{n}.b", sd[f"time_embedding.{n}.bias"])
-        self.has_cond = bool(cfg.get("time_cond_proj_dim"))
         if self.has_cond:
             self._put("te.cond.w", sd["time_embedding.cond_proj.weight"])
-        self.has_added = bool(cfg.get("addition_time_embed_dim"))       # SDXL "text_time" embedding
-        if self.has_added:
-            for n in ("linear_1", "linear_2"):
-                self._put(f"add.{n}.w", sd[f"add_embedding.{n}.weight"])
-                self._put(f"add.{n}.b", sd[f"add_embedding.{n}.bias"])
-            self.added_dim = cfg["projection_class_embeddings_input_dim"]
+
+    def _pack_down_mid(self, sd, temb_list, kv_list):
+        cfg = self.cfg
+        nb = len(cfg["block_out_channels"])
         for i in range(nb):
             for j in range(cfg["layers_per_block"]):
                 self._pack_resnet(sd, f"down_blocks.{i}.resnets.{j}", temb_list)
@@ -242,22 +243,8 @@ class UNetHip(_Net):
         self._pack_resnet(sd, "mid_block.resnets.0", temb_list)
         self._pack_transformer(sd, "mid_block.attentions.0", kv_list, depth_at(cfg, nb - 1), heads_at(cfg, nb - 1))
         self._pack_resnet(sd, "mid_block.resnets.1", temb_list)
-        up_attn = tuple(reversed(cfg["down_attn"]))
-        for i in range(nb):
-            for j in range(cfg["layers_per_block"] + 1):
-                self._pack_resnet(sd, f"up_blocks.{i}.resnets.{j}", temb_list)
-                if up_attn[i]:
-                    self._pack_transformer(sd, f"up_blocks.{i}.attentions.{j}", kv_list, depth_at(cfg, nb - 1 - i), heads_at(cfg, nb - 1 - i))
-            if i < nb - 1:
-                p = f"up_blocks.{i}.upsamplers.0.conv"
-                self._put(p + ".w", (pack_conv3x3_up2 if UPS_PHASES else pack_conv3x3)(sd[p + ".weight"]))
-                if UPS_PHASES:       # plain 3x3 layout too: upsampling to an odd-sized skip cannot use the pre-summed phase weights
-                    self._put(p + ".w3", pack_conv3x3(sd[p + ".weight"]))
-                self._put(p + ".b", sd[p + ".bias"])
-        self._put("conv_norm_out.g", sd["conv_norm_out.weight"])
-        self._put("conv_norm_out.b", sd["conv_norm_out.bias"])
-        self._put("conv_out.w", pack_conv3x3(sd["conv_out.weight"]))
-        self._put("conv_out.b", sd["conv_out.bias"])
+
+    def _pack_tables(self, temb_list, kv_list):
         # all ResnetBlock2D.time_emb_proj stacked into one [sum(Cout), temb] matrix -> one launch per step
         self.temb_off, off = {}, 0
         for p, wt, bt in temb_list:
@@ -454,25 +441,14 @@ class UNetHip(_Net):
         ops.gemm(h, w[p + ".proj_out.w"], out, bias=w[p + ".proj_out.b"], res=x, stats=out_st, img_rows=HW)
         return out, out_st
 
-    def forward(self, lat, t, kv_all, wemb, B, h, w_, eps_out, taps=None, aug=None, ta=None):
-        """lat fp32 [B,4,h,w] -> eps_out fp32 [B,h,w,4] (pixel-major).  aug: SDXL additional embedding (encode_added).
-        ta: this step's rows of time_embed_all (the sampler computes all steps ahead of the loop); None: computed here."""
+    def _down_mid(self, x, B, H, W, kv_all, ta, tap):
+        """The down blocks and the mid block from conv_in's output ``x`` (role skip0).
+        -> (x, st, skips [(tensor, channels, fused statistics or None)], sizes, ch, H, W)."""
         cfg, wt = self.cfg, self.w
         boc = cfg["block_out_channels"]
         nb = len(boc)
-        if ta is None:
-            ta = self.time_embed(t, wemb, B, aug)
-        H, W = h, w_
-        x = self.buf.get("skip0", B * H * W, boc[0])
-        ops.conv3x3_c4(lat, wt["conv_in.w"], x, B, H, W, boc[0], bias=wt["conv_in.b"])
         skips = [(x, boc[0], None)]          # (tensor, channels, fused statistics or None)
         ch, ns, st = boc[0], 1, None
-
-        def tap(name, t_, C, H_, W_):
-            if taps is not None:
-                taps[name] = t_.reshape(B, H_, W_, C).permute(0, 3, 1, 2).float().cpu()
-
-        tap("conv_in", x, ch, H, W)
         sizes = [(H, W)]                      # spatial size per level: a stride-2, padding-1 conv gives ceil(n / 2)
         for i in range(nb):
             for j in range(cfg["layers_per_block"]):
@@ -503,6 +479,84 @@ class UNetHip(_Net):
                                  heads=heads_at(cfg, nb - 1), depth=depth_at(cfg, nb - 1))
         x, st = self._res("mid_block.resnets.1", x, ch, ch, B, H, W, ta, out_role="cur", x_st=st)
         tap("mid_block.resnets.1", x, ch, H, W)
+        return x, st, skips, sizes, ch, H, W
+
+
+# ==================================================================================================
+class UNetHip(_UNetEncoder):
+    def __init__(self, sd: dict, cfg: dict | None = None, device="cuda"):
+        super().__init__(device)
+        cfg = unet_config(cfg)
+        self._init_encoder(cfg)
+        boc = cfg["block_out_channels"]
+        nb = len(boc)
+        temb_list, kv_list = [], []
+        self._pack_head(sd)
+        if self.has_added:
+            for n in ("linear_1", "linear_2"):
+                self._put(f"add.{n}.w", sd[f"add_embedding.{n}.weight"])
+                self._put(f"add.{n}.b", sd[f"add_embedding.{n}.bias"])
+            self.added_dim = cfg["projection_class_embeddings_input_dim"]
+        self._pack_down_mid(sd, temb_list, kv_list)
+        up_attn = tuple(reversed(cfg["down_attn"]))
+        for i in range(nb):
+            for j in range(cfg["layers_per_block"] + 1):
+                self._pack_resnet(sd, f"up_blocks.{i}.resnets.{j}", temb_list)
+                if up_attn[i]:
+                    self._pack_transformer(sd, f"up_blocks.{i}.attentions.{j}", kv_list, depth_at(cfg, nb - 1 - i), heads_at(cfg, nb - 1 - i))
+            if i < nb - 1:
+                p = f"up_blocks.{i}.upsamplers.0.conv"
+                self._put(p + ".w", (pack_conv3x3_up2 if UPS_PHASES else pack_conv3x3)(sd[p + ".weight"]))
+                if UPS_PHASES:       # plain 3x3 layout too: upsampling to an odd-sized skip cannot use the pre-summed phase weights
+                    self._put(p + ".w3", pack_conv3x3(sd[p + ".weight"]))
+                self._put(p + ".b", sd[p + ".bias"])
+        self._put("conv_norm_out.g", sd["conv_norm_out.weight"])
+        self._put("conv_norm_out.b", sd["conv_norm_out.bias"])
+        self._put("conv_out.w", pack_conv3x3(sd["conv_out.weight"]))
+        self._put("conv_out.b", sd["conv_out.bias"])
+        self._pack_tables(temb_list, kv_list)
+
+    def forward(self, lat, t, kv_all, wemb, B, h, w_, eps_out, taps=None, aug=None, ta=None, control=None):
+        """lat fp32 [B,4,h,w] -> eps_out fp32 [B,h,w,4] (pixel-major).  aug: SDXL additional embedding (encode_added).
+        ta: this step's rows of time_embed_all (the sampler computes all steps ahead of the loop); None: computed here.
+        control: (ControlNetHip, its 12 down features [(tensor, channels, _)], its mid feature, conditioning scale) of this step
+        (ControlNetHip.forward); None: exactly the launches of a plain pass."""
+        cfg, wt = self.cfg, self.w
+        boc = cfg["block_out_channels"]
+        nb = len(boc)
+        if ta is None:
+            ta = self.time_embed(t, wemb, B, aug)
+        H, W = h, w_
+        x = self.buf.get("skip0", B * H * W, boc[0])
+        ops.conv3x3_c4(lat, wt["conv_in.w"], x, B, H, W, boc[0], bias=wt["conv_in.b"])
+
+        def tap(name, t_, C, H_, W_):
+            if taps is not None:
+                taps[name] = t_.reshape(B, H_, W_, C).permute(0, 3, 1, 2).float().cpu()
+
+        tap("conv_in", x, boc[0], H, W)
+        x, st, skips, sizes, ch, H, W = self._down_mid(x, B, H, W, kv_all, ta, tap)
+        if control is not None:
+            # ControlNet residuals: skip_i + s (W_i f_i + b_i) as ONE GEMM per residual (the zero convolution with the skip as
+            # its res= operand), into a buffer of its own -- the encoder above ran on the unmodified tensors, as in diffusers,
+            # where the residuals are added to down_block_res_samples after the down blocks.  The modified tensors carry no
+            # fused statistics: the consuming GroupNorm computes its own.
+            cn, feats, mid_f, cscale = control
+            lv, k = [], 0
+            for i in range(nb):                                      # level of every skip, for its spatial size
+                lv += [i] * (cfg["layers_per_block"] + (1 if i == 0 else 0))
+                if i < nb - 1:
+                    lv.append(i + 1)
+            for k, (s, sc, _) in enumerate(skips):
+                Hs, Ws = sizes[lv[k]]
+                o = self.buf.get(f"ctl_skip{k}", s.shape[0], sc)
+                cn.inject(k, feats[k][0], s, o, cscale, Hs * Ws, B, Hs, Ws, taps)
+                skips[k] = (o, sc, None)
+                tap(f"ctl.skip.{k}", o, sc, Hs, Ws)
+            o = self.buf.get("ctl_mid", x.shape[0], ch)
+            cn.inject("mid", mid_f, x, o, cscale, H * W, B, H, W, taps)
+            x, st = o, None
+            tap("ctl.mid", x, ch, H, W)
         rboc = tuple(reversed(boc))
         up_attn = tuple(reversed(cfg["down_attn"]))
         for i in range(nb):
@@ -535,6 +589,83 @@ class UNetHip(_Net):
         hn = self.buf.get("gn", B * H * W, ch)
         self._norm_conv_out(x, "conv_norm_out", st, hn, eps_out, B, H, W, ch, cfg["out_channels"], cfg["norm_eps"], mode=0)
         return eps_out
+
+
+
+# ==================================================================================================
+class ControlNetHip(_UNetEncoder):
+    """diffusers' ControlNetModel on the UNet's kernels: the hint stack (csrc/controlnet.hip) once per request, then per step
+    conv_in(latents) + hint embedding, the down and mid blocks (the shared _UNetEncoder launches, this net's own weights, time
+    embedding and cross-attention K/V), and -- issued by UNetHip.forward through ``inject`` -- the thirteen zero convolutions."""
+
+    def __init__(self, sd: dict, cfg: dict | None = None, unet_cfg: dict | None = None, device="cuda"):
+        super().__init__(device)
+        from .weights import check_controlnet_matches, controlnet_config
+        cfg = controlnet_config(unet_cfg) if cfg is None else dict(cfg)
+        check_controlnet_matches(cfg, unet_config(unet_cfg))
+        cfg = unet_config(cfg)
+        cfg["time_cond_proj_dim"] = None
+        self._init_encoder(cfg)
+        self.cond_channels = cc = tuple(cfg["conditioning_embedding_out_channels"])
+        e = "controlnet_cond_embedding"
+        names = [e + ".conv_in"] + [f"{e}.blocks.{i}" for i in range(2 * (len(cc) - 1))] + [e + ".conv_out"]
+        for i, n in enumerate(names):
+            self._put(f"hint.{i}.w", pack_conv3x3(sd[n + ".weight"]))
+            self._put(f"hint.{i}.b", sd[n + ".bias"])
+        temb_list, kv_list = [], []
+        self._pack_head(sd)
+        self._pack_down_mid(sd, temb_list, kv_list)
+        self._pack_tables(temb_list, kv_list)
+        from .weights import controlnet_skip_channels
+        self.n_down = len(controlnet_skip_channels(cfg))
+        for i in list(range(self.n_down)) + ["mid"]:
+            n = f"controlnet_down_blocks.{i}" if i != "mid" else "controlnet_mid_block"
+            self._put(f"zero.{i}.w", pack_conv1x1(sd[n + ".weight"]))
+            self._put(f"zero.{i}.b", sd[n + ".bias"])
+
+    def embed_hint(self, hint_u8, B, H, W, out):
+        """hint uint8 [B,H,W,3] (full output resolution) -> out fp16 [B * H/8 * W/8, block_out_channels[0]].  Depends on the hint
+        alone: once per request, ahead of the step loop."""
+        w, cc = self.w, self.cond_channels
+        x = self.buf.get("hint0", B * H * W, cc[0])
+        ops.hint_conv_u8(hint_u8, w["hint.0.w"], x, B, H, W, cc[0], bias=w["hint.0.b"], silu=True)
+        for i in range(2 * (len(cc) - 1)):
+            cin, cout, stride = cc[i // 2], cc[i // 2 + (i & 1)], 1 + (i & 1)
+            Ho, Wo = ((H + 1) // 2, (W + 1) // 2) if stride == 2 else (H, W)
+            y = self.buf.get(f"hint{i + 1}", B * Ho * Wo, cout)
+            ops.hint_conv(x, w[f"hint.{i + 1}.w"], y, B, H, W, cin, cout, bias=w[f"hint.{i + 1}.b"], stride=stride, silu=True)
+            x, H, W = y, Ho, Wo
+        # 256 -> 320 at latent resolution is an implicit-GEMM shape (channels multiples of 64): the UNet's conv3x3
+        n = 2 * len(cc) - 1
+        ops.conv3x3(x, w[f"hint.{n}.w"], out, B, H, W, cc[-1], self.cfg["block_out_channels"][0], bias=w[f"hint.{n}.b"])
+        return out
+
+    def forward(self, lat, t, kv_all, B, h, w_, hint_emb, taps=None, ta=None):
+        """lat fp32 [B,4,h,w], hint_emb fp16 [B*h*w, boc0] -> (12 down features [(tensor, channels, stats)], mid feature)."""
+        boc = self.cfg["block_out_channels"]
+        if ta is None:
+            ta = self.time_embed(t, None, B)
+        x = self.buf.get("skip0", B * h * w_, boc[0])
+        ops.conv3x3_c4_res(lat, self.w["conv_in.w"], x, B, h, w_, boc[0], bias=self.w["conv_in.b"], res=hint_emb)
+
+        def tap(name, t_, C, H_, W_):
+            if taps is not None:
+                taps["cn." + name] = t_.reshape(B, H_, W_, C).permute(0, 3, 1, 2).float().cpu()
+
+        tap("conv_in", x, boc[0], h, w_)
+        x, _, skips, _, _, _, _ = self._down_mid(x, B, h, w_, kv_all, ta, tap)
+        return skips, x
+
+    def inject(self, i, feat, skip, out, scale, img_rows, B, H, W, taps=None):
+        """out = skip + scale (W_i feat + b_i): zero convolution, scale and residual add in one GEMM launch (the epilogue's order is
+        out_scale * (sum + bias) + res)."""
+        ops.gemm(feat, self.w[f"zero.{i}.w"], out, bias=self.w[f"zero.{i}.b"], res=skip, out_scale=float(scale), img_rows=img_rows)
+        if taps is not None:          # the residual on its own, for the tests only
+            C = out.shape[1]
+            r = torch.empty_like(out)
+            ops.gemm(feat, self.w[f"zero.{i}.w"], r, bias=self.w[f"zero.{i}.b"], out_scale=float(scale), img_rows=img_rows)
+            taps[f"ctl.res.{i}"] = r.reshape(B, H, W, C).permute(0, 3, 1, 2).float().cpu()
+            taps[f"ctl.feat.{i}"] = feat.reshape(B, H, W, C).permute(0, 3, 1, 2).float().cpu()
 
 
 def scale_vae_residual_stream(sd: dict, cfg: dict, s: float) -> dict:

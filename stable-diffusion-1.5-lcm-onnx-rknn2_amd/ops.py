@@ -309,6 +309,30 @@ def conv3x3_c4(lat_f32, w, out, B, H, W, Cout, *, bias=None, pre_w=None, pre_b=N
     return out
 
 
+def conv3x3_c4_res(lat_f32, w, out, B, H, W, Cout, *, bias=None, res):
+    """conv3x3_c4 + res (fp16 [B*H*W, Cout]) in one launch: the ControlNet's conv_in(latents) + hint embedding."""
+    L = _lib.load()
+    rc = L.lcm_conv3x3_c4_res_f32in(_p(lat_f32), _p(w), _p(bias), _p(res), _p(out), B, H, W, Cout, _stream())
+    _lib.check(rc, "lcm_conv3x3_c4_res_f32in")
+    return out
+
+
+def hint_conv_u8(img_u8, w, out, B, H, W, Cout, *, bias=None, silu=True):
+    """First layer of the ControlNet hint stack: uint8 RGB [B,H,W,3] -> fp16 [B*H*W, Cout], x / 255 applied in the kernel
+    (include/lcm_hip.h, lcm_hint_conv_u8).  w: fp16 [Cout][27] (packing.pack_conv3x3)."""
+    L = _lib.load()
+    _lib.check(L.lcm_hint_conv_u8(_p(img_u8), _p(w), _p(bias), _p(out), B, H, W, Cout, 1 if silu else 0, _stream()), "lcm_hint_conv_u8")
+    return out
+
+
+def hint_conv(x, w, out, B, H, W, Cin, Cout, *, bias=None, stride=1, silu=True):
+    """A narrow layer of the hint stack (Cin 16 / 32 / 96): fp16 [B*H*W, Cin] -> [B*Ho*Wo, Cout], stride 2 gives ceil(n / 2)."""
+    L = _lib.load()
+    _lib.check(L.lcm_hint_conv_f16(_p(x), _p(w), _p(bias), _p(out), B, H, W, Cin, Cout, int(stride), 1 if silu else 0, _stream()),
+               "lcm_hint_conv_f16")
+    return out
+
+
 def conv3x3_smalln(x, w, out, B, H, W, Cin, Cout, *, bias=None, mode=0, out_f32=None, gn_scale=None, gn_shift=None, silu=True):
     """gn_scale / gn_shift (groupnorm_tables_from_stats): x is the raw tensor, GroupNorm-apply (+SiLU) fused into the staging."""
     L = _lib.load()

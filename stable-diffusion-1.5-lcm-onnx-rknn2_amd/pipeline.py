@@ -20,7 +20,7 @@ import torch
 from . import ops
 from .config import TEXT_SEQ_LEN, VAE_SCALE_FACTOR
 from .lib import LcmHipError
-from .model import UNetHip, VAEDecoderHip
+from .model import ControlNetHip, UNetHip, VAEDecoderHip
 from .scheduler import LCMSchedule
 
 
@@ -102,17 +102,20 @@ class _Lane:
         ops.set_stream_workspace(self.side, self.side_ws)
         self.unet.side_stream = self.side
         self.vae.side_stream = self.side
+        self.controlnet = None        # this lane's executor of the pipeline's ControlNet (LcmHipPipeline.lane_controlnet)
+        self._controlnet_of = None
 
 
 class _Plan:
     """Buffers + captured graph for one (B, h, w, steps, cfg) key.  refine = (strength, passes to run, starts from cached
     latents) makes it the plan of a refinement chain (LcmHipPipeline._enqueue_refine); None: the plain sampler."""
 
-    def __init__(self, pipe, B, h, w, steps, do_cfg, lane=None, refine=None):
+    def __init__(self, pipe, B, h, w, steps, do_cfg, lane=None, refine=None, control=None):
         # Every zero-fill below must be ordered before the first use on the lane's (non-blocking) stream: allocate
         # under that stream, or a fill still queued on the null stream can land AFTER the request's uploads.
         self.lane = lane if lane is not None else pipe.lanes[0]
         self.refine = refine
+        self.control = control        # conditioning scale of a ControlNet plan (baked into the captured GEMMs); None: no hint
         with torch.cuda.stream(self.lane.stream):
             self._init(pipe, B, h, w, steps, do_cfg)
 
@@ -139,6 +142,13 @@ class _Plan:
         self.eps = torch.zeros(UB, h, w, 4, dtype=torch.float32, device=dev)
         self.rgb = torch.zeros(B, h * VAE_SCALE_FACTOR, w * VAE_SCALE_FACTOR, 3, dtype=torch.uint8, device=dev)
         self.pool8 = torch.zeros(B, 4, 8, 8, dtype=torch.float16, device=dev)
+        if self.control is not None:
+            # the request's hint: a fixed device buffer of this plan (i.e. of this lane) that every replay uploads into, and
+            # its embedding, written once per request by the hint stack inside the captured graph
+            H8, W8 = h * VAE_SCALE_FACTOR, w * VAE_SCALE_FACTOR
+            self.hint = torch.zeros(B, H8, W8, 3, dtype=torch.uint8, device=dev)
+            self.h_hint = torch.zeros(B, H8, W8, 3, dtype=torch.uint8).pin_memory()
+            self.hint_emb = torch.zeros(UB * h * w, pipe.unet.cfg["block_out_channels"][0], dtype=torch.float16, device=dev)
         self.img_f32 = None
         self.guidance = 1.0
         self.graph = None
@@ -164,6 +174,7 @@ class LcmHipPipeline:
         self.use_graph = use_graph
         self._tuned_keys = set()
         self._build_lock = threading.RLock()      # tuning / eager warm-up / capture of a plan: one lane at a time
+        self.controlnet = None
         self.lanes = [_Lane(self, 0, self.unet, self.vae)]
         self.stream = self.lanes[0].stream
         self._plans = self.lanes[0].plans
@@ -192,6 +203,29 @@ class LcmHipPipeline:
                 self.lanes.append(_Lane(self, len(self.lanes), self.unet.view(), self.vae.view()))
         return self.lanes[index]
 
+    def set_controlnet(self, sd, cfg=None):
+        """Load a ControlNet (diffusers ControlNetModel state dict + config) beside the UNet; None releases it.  It must fit
+        the UNet (weights.check_controlnet_matches raises otherwise).  Plans with a hint are dropped: they bake its pointers in."""
+        with self._build_lock:
+            for L in self.lanes:
+                for key in [k for k, P in L.plans.items() if P.control is not None]:
+                    P = L.plans.pop(key)
+                    if P.graph is not None:
+                        P.graph.close()
+                L.controlnet = L._controlnet_of = None
+            self.controlnet = None if sd is None else ControlNetHip(sd, cfg, self.unet.cfg, self.device)
+        return self.controlnet
+
+    def lane_controlnet(self, L: _Lane):
+        """The lane's executor of the ControlNet: weights shared, scratch of its own (like the UNet's views)."""
+        if self.controlnet is None:
+            raise LcmHipError("this request carries a ControlNet hint but no ControlNet is loaded (set_controlnet)")
+        if L._controlnet_of is not self.controlnet:
+            L.controlnet = self.controlnet if L.index == 0 else self.controlnet.view()
+            L.controlnet.side_stream = L.side
+            L._controlnet_of = self.controlnet
+        return L.controlnet
+
     def _enqueue(self, P: _Plan, guidance: float, want_float=False, taps=None):
         """Enqueue the whole sampler on the current stream (this is what gets captured)."""
         if P.refine is not None:
@@ -210,9 +244,27 @@ class LcmHipPipeline:
         # the time-embedding MLP + all time_emb_proj of EVERY step ahead of the loop (they depend on the schedule and the
         # request's guidance only): 5 launches per pass instead of 4 per step
         ta_all = unet.time_embed_all([int(t) for t in ts], wemb, UB, aug) if len(ts) <= unet.MAX_HOISTED_STEPS else None
+        cn = None
+        if P.control is not None:
+            # ControlNet: the hint embedding ONCE per request (it depends on the hint alone), repeated for the unconditional
+            # half under classifier-free guidance (diffusers' guess_mode=False); its own cross-attention K/V and time embeddings
+            cn = self.lane_controlnet(P.lane)
+            n1 = B * h * w
+            cn.embed_hint(P.hint, B, h * VAE_SCALE_FACTOR, w * VAE_SCALE_FACTOR, P.hint_emb[:n1])
+            if P.do_cfg:
+                P.hint_emb[n1:].copy_(P.hint_emb[:n1])
+            if taps is not None:
+                taps["cn.hint_emb"] = P.hint_emb[:n1].reshape(B, h, w, -1).permute(0, 3, 1, 2).float().cpu()
+            kv_c = cn.encode_context(P.ehs, UB)
+            ta_c = cn.time_embed_all([int(t) for t in ts], None, UB) if len(ts) <= cn.MAX_HOISTED_STEPS else None
         for i, t in enumerate(ts):
+            control = None
+            if cn is not None:
+                feats, mid_f = cn.forward(P.lat, int(t), kv_c, UB, h, w, P.hint_emb, taps=taps if i == 0 else None,
+                                          ta=ta_c[i * UB:(i + 1) * UB] if ta_c is not None else None)
+                control = (cn, feats, mid_f, P.control)
             unet.forward(P.lat, int(t), kv, wemb, UB, h, w, P.eps, taps=taps if i == 0 else None, aug=aug,
-                         ta=ta_all[i * UB:(i + 1) * UB] if ta_all is not None else None)
+                         ta=ta_all[i * UB:(i + 1) * UB] if ta_all is not None else None, control=control)
             coef, last = self.sched.step_coefficients(ts, i)
             noise = P.noise[min(i, P.noise.shape[0] - 1)]
             pred = self.sched.prediction_type
@@ -283,18 +335,21 @@ class LcmHipPipeline:
         vae.decode(state, B, h, w, P.rgb, img_f32=P.img_f32 if want_float else None, taps=taps)
         return state
 
-    def plan(self, B, h, w, steps, do_cfg=False, guidance=None, lane=0, refine=None) -> _Plan:
+    def plan(self, B, h, w, steps, do_cfg=False, guidance=None, lane=0, refine=None, control=None) -> _Plan:
         # classifier-free guidance bakes the guidance value into the captured step kernels: one plan per value
         key = (B, h, w, steps, do_cfg, round(float(guidance), 4) if do_cfg and guidance is not None else None)
         if refine is not None:                       # (d, passes to run, starts from cached latents): a chain of its own
             key = key + (round(float(refine[0]), 6), int(refine[1]), bool(refine[2]))
+        if control is not None:                      # a ControlNet plan: "control" + the conditioning scale its GEMMs bake in
+            key = key + ("control", round(float(control), 6))
         L = self.lane(lane)
         P = L.plans.get(key)
         if P is None:
             with self._build_lock:
                 P = L.plans.get(key)
                 if P is None:
-                    P = _Plan(self, B, h, w, steps, do_cfg, L, refine=refine)
+                    P = _Plan(self, B, h, w, steps, do_cfg, L, refine=refine,
+                              control=None if control is None else round(float(control), 6))
                     L.plans[key] = P
         return P
 
@@ -332,6 +387,7 @@ class LcmHipPipeline:
         """Drop the captured graphs and take this pipeline's workspaces out of the library's per-stream table (the library
         keeps raw pointers).  Idempotent; also run when the pipeline is collected."""
         lanes, self.lanes = getattr(self, "lanes", []), []
+        self.controlnet = None
         for L in lanes:
             for P in L.plans.values():
                 if P.graph is not None:
@@ -357,7 +413,7 @@ class LcmHipPipeline:
     @torch.inference_mode()
     def generate(self, prompt_embeds, seeds, width, height, steps, guidance_scale=1.0, negative_embeds=None,
                  want_float=False, taps=None, latents=None, added=None, negative_added=None, noises=None, lane=0,
-                 strength=None, passes=0, start=None):
+                 strength=None, passes=0, start=None, control=None):
         """prompt_embeds: [B,77,ctx] (any float dtype, host or device); seeds: B ints.  noises: optional per-request
         ``draw_noise(seed, h, w, steps - 1, init_noise_sigma)`` results drawn ahead by the callers (the worker's pool
         threads draw them in parallel, off the dispatcher's serial path); None: drawn here from the seeds.
@@ -370,6 +426,10 @@ class LcmHipPipeline:
         [4,h,w]]): the chain starts from these x^k (0 <= k < passes) and runs passes - k passes; the draws of the passes
         left out are skipped, so the result does not depend on where the chain started.  The result then carries
         ``xk_first`` and ``xk`` (device fp32 [n,B,4,h,w]: x^xk_first ... x^passes) and ``unet_evals``.
+        control = (hint uint8 [B,H,W,3] at the request's size, conditioning_scale): ControlNet-conditioned generation with the
+        ControlNet of set_controlnet.  The scale is part of the plan key (the captured GEMMs carry it as a scalar argument);
+        the hint is uploaded per request into the plan's fixed buffer.  Not combined with passes.  The result then carries
+        ``controlnet_evals``.
         Returns dict(rgb uint8 [B,H,W,3] (host), latents fp32 [B,4,h,w] (host), pool8 fp16 [B,4,8,8] (host))."""
         torch.cuda.set_device(self.device)        # the pool may call from a thread other than the constructing one
         pe = torch.as_tensor(prompt_embeds)
@@ -398,7 +458,20 @@ class LcmHipPipeline:
             skip = steps * (k0 + 1) - 1 if k0 is not None else 0
         elif strength is not None and float(strength) != 1.0:
             raise LcmHipError("strength needs passes >= 1")
-        P = self.plan(B, h, w, steps, do_cfg, guidance_scale, lane=lane, refine=refine)
+        hint = cscale = None
+        if control is not None:
+            if refine is not None:
+                raise LcmHipError("a ControlNet hint is not combined with refinement passes")
+            if self.controlnet is None:
+                raise LcmHipError("this request carries a ControlNet hint but no ControlNet is loaded (set_controlnet)")
+            hint, cscale = control
+            cscale = float(cscale)
+            if not 0.0 <= cscale <= 2.0:
+                raise LcmHipError(f"controlnet conditioning scale {cscale} outside [0, 2]")
+            hint = torch.as_tensor(hint)
+            if hint.dtype != torch.uint8 or tuple(hint.shape) != (B, height, width, 3):
+                raise LcmHipError(f"ControlNet hint must be uint8 [B={B}, H={height}, W={width}, 3], got {hint.dtype} {tuple(hint.shape)}")
+        P = self.plan(B, h, w, steps, do_cfg, guidance_scale, lane=lane, refine=refine, control=cscale)
         stream = P.lane.stream
         with torch.cuda.stream(stream):
             # ---- host-side request state -> device (outside the graph) ----
@@ -417,6 +490,9 @@ class LcmHipPipeline:
                     P.h_noise[i, b].copy_(n[0])
             P.lat0.copy_(P.h_lat, non_blocking=True)
             P.noise.copy_(P.h_noise, non_blocking=True)
+            if hint is not None:
+                P.h_hint.copy_(hint)
+                P.hint.copy_(P.h_hint, non_blocking=True)
             if refine is not None and refine[2]:
                 for b in range(B):
                     P.xk[0, b].copy_(start[1][b].reshape(4, h, w), non_blocking=True)
@@ -471,6 +547,8 @@ class LcmHipPipeline:
         if refine is not None:
             out["xk"], out["xk_first"] = xk, passes - refine[1]
             out["unet_evals"] = steps * (refine[1] + (0 if refine[2] else 1))
+        if control is not None:
+            out["controlnet_evals"] = steps
         if want_float:
             out["image"] = P.img_f32.cpu().numpy()   # NHWC float, pre-clamp
         return out

@@ -203,6 +203,191 @@ def synthetic_vae(cfg=None, seed=1):
 
 
 # ---------------------------------------------------------------------------------------
+# ControlNet (diffusers ControlNetModel): the UNet's encoder half + hint embedding + thirteen 1x1 zero convolutions
+# ---------------------------------------------------------------------------------------
+CONTROLNET_COND_CHANNELS = (16, 32, 96, 256)          # conditioning_embedding_out_channels of every published SD ControlNet
+
+
+def controlnet_config(unet_cfg: dict | None = None, overrides: dict | None = None) -> dict:
+    """The ControlNet that goes with a UNet: its encoder's numbers, no guidance embedding (ControlNetModel has none), and the
+    hint embedding's widths."""
+    c = unet_config(unet_cfg)
+    c["time_cond_proj_dim"] = None
+    c["conditioning_embedding_out_channels"] = CONTROLNET_COND_CHANNELS
+    c["conditioning_channels"] = 3
+    if overrides:
+        c.update(overrides)
+    return c
+
+
+def controlnet_skip_channels(cfg: dict) -> list:
+    """Channels of the 12 (SD1.5 / SD 2.x) down-path feature maps, in the order the UNet keeps its skips."""
+    boc = cfg["block_out_channels"]
+    out = [boc[0]]
+    for i in range(len(boc)):
+        out += [boc[i]] * cfg["layers_per_block"]
+        if i < len(boc) - 1:
+            out.append(boc[i])
+    return out
+
+
+def controlnet_param_spec(cfg: dict | None = None):
+    cfg = controlnet_config(cfg) if cfg is None or "conditioning_embedding_out_channels" not in cfg else cfg
+    boc = cfg["block_out_channels"]
+    temb = boc[0] * 4
+    ctx = cfg["cross_attention_dim"]
+    cc = tuple(cfg["conditioning_embedding_out_channels"])
+    e = "controlnet_cond_embedding"
+    yield e + ".conv_in.weight", (cc[0], cfg.get("conditioning_channels", 3), 3, 3), "w"
+    yield e + ".conv_in.bias", (cc[0],), "bias"
+    for i in range(len(cc) - 1):                      # blocks 2i: cc[i] -> cc[i]; 2i + 1: cc[i] -> cc[i + 1], stride 2
+        yield f"{e}.blocks.{2 * i}.weight", (cc[i], cc[i], 3, 3), "w"
+        yield f"{e}.blocks.{2 * i}.bias", (cc[i],), "bias"
+        yield f"{e}.blocks.{2 * i + 1}.weight", (cc[i + 1], cc[i], 3, 3), "w"
+        yield f"{e}.blocks.{2 * i + 1}.bias", (cc[i + 1],), "bias"
+    yield e + ".conv_out.weight", (boc[0], cc[-1], 3, 3), "w_res"
+    yield e + ".conv_out.bias", (boc[0],), "bias"
+    yield "conv_in.weight", (boc[0], cfg["in_channels"], 3, 3), "w"
+    yield "conv_in.bias", (boc[0],), "bias"
+    yield "time_embedding.linear_1.weight", (temb, boc[0]), "w"
+    yield "time_embedding.linear_1.bias", (temb,), "bias"
+    yield "time_embedding.linear_2.weight", (temb, temb), "w"
+    yield "time_embedding.linear_2.bias", (temb,), "bias"
+    nb = len(boc)
+    lin = bool(cfg.get("use_linear_projection"))
+    ch = boc[0]
+    for i in range(nb):
+        for j in range(cfg["layers_per_block"]):
+            yield from _resnet(f"down_blocks.{i}.resnets.{j}", ch, boc[i], temb)
+            ch = boc[i]
+            if cfg["down_attn"][i]:
+                yield from _transformer(f"down_blocks.{i}.attentions.{j}", ch, ctx, depth_at(cfg, i), lin)
+        if i < nb - 1:
+            yield f"down_blocks.{i}.downsamplers.0.conv.weight", (ch, ch, 3, 3), "w"
+            yield f"down_blocks.{i}.downsamplers.0.conv.bias", (ch,), "bias"
+    yield from _resnet("mid_block.resnets.0", ch, ch, temb)
+    yield from _transformer("mid_block.attentions.0", ch, ctx, depth_at(cfg, nb - 1), lin)
+    yield from _resnet("mid_block.resnets.1", ch, ch, temb)
+    for i, c in enumerate(controlnet_skip_channels(cfg)):
+        yield f"controlnet_down_blocks.{i}.weight", (c, c, 1, 1), "zero"
+        yield f"controlnet_down_blocks.{i}.bias", (c,), "zero_bias"
+    yield "controlnet_mid_block.weight", (ch, ch, 1, 1), "zero"
+    yield "controlnet_mid_block.bias", (ch,), "zero_bias"
+
+
+# Standard deviation of the synthetic "zero" convolutions in units of fan_in^-0.5.  Chosen on the CPU reference so that the hint
+# moves the decoded 64^2 / 128^2 / 256^2 image by a mean |d| of more than ten times the 1e-2 parity tolerance: 0.5 gives 0.056 ..
+# 0.060, 1.0 gives 0.099 .. 0.101, 1.5 gives 0.123 .. 0.125 (tests/test_controlnet_cpu.py asserts it).
+SYNTHETIC_ZERO_CONV_SCALE = 1.5
+
+
+def synthetic_controlnet(cfg=None, seed=7, zero=False, zero_scale=SYNTHETIC_ZERO_CONV_SCALE):
+    """Seeded synthetic ControlNet of the UNet config ``cfg`` (None: SD1.5), by the scaling rules of synthetic_state_dict.
+    The zero convolutions are NOT zero: N(0, zero_scale^2 / fan_in) weights and 0.02-sigma biases.  zero=True: the variant
+    with truly zero controlnet_down_blocks / controlnet_mid_block (an untrained ControlNet: the plain request's picture)."""
+    ccfg = controlnet_config(cfg) if cfg is None or "conditioning_embedding_out_channels" not in cfg else cfg
+    spec = list(controlnet_param_spec(ccfg))
+    sd = synthetic_state_dict([(n, s, k) for n, s, k in spec if not k.startswith("zero")], seed)
+    g = torch.Generator(device="cpu").manual_seed(seed + 1000)
+    for n, shape, kind in spec:
+        if kind == "zero":
+            t = torch.randn(shape, generator=g, dtype=torch.float32) * (zero_scale * shape[1] ** -0.5)
+        elif kind == "zero_bias":
+            t = 0.02 * torch.randn(shape, generator=g, dtype=torch.float32)
+        else:
+            continue
+        sd[n] = (torch.zeros(shape) if zero else t).to(torch.float16)
+    return sd
+
+
+def _controlnet_cfg_from_json(j: dict) -> dict:
+    base = controlnet_config()
+    out = dict(base)
+    for k in base:
+        if k in j and j[k] is not None:
+            out[k] = tuple(j[k]) if isinstance(j[k], list) else j[k]
+    out["time_cond_proj_dim"] = None
+    if "down_block_types" in j:
+        out["down_attn"] = tuple("CrossAttn" in t for t in j["down_block_types"])
+    if j.get("addition_embed_type") or j.get("addition_time_embed_dim"):
+        out["addition_time_embed_dim"] = j.get("addition_time_embed_dim") or 256
+    return out
+
+
+def _controlnet_cfg_from_tensors(sd: dict) -> dict:
+    """A bare .safetensors says nothing but shapes: widths from conv_in / the resnets, context width and head layout from the
+    attention weights (SD 2.x: linear projections, 64-wide heads; SD1.5: 1x1-conv projections, 8 heads)."""
+    try:
+        boc = (sd["conv_in.weight"].shape[0],) + tuple(sd[f"down_blocks.{i}.resnets.0.conv1.weight"].shape[0] for i in (1, 2, 3))
+        ctx = sd["down_blocks.0.attentions.0.transformer_blocks.0.attn2.to_k.weight"].shape[1]
+        lin = sd["down_blocks.0.attentions.0.proj_in.weight"].ndim == 2
+        cc = (sd["controlnet_cond_embedding.conv_in.weight"].shape[0],) + tuple(
+            sd[f"controlnet_cond_embedding.blocks.{2 * i + 1}.weight"].shape[0] for i in range(3))
+    except KeyError as e:
+        if any(k.startswith("add_embedding.") for k in sd):
+            raise RuntimeError("SDXL ControlNets are not supported (the file carries add_embedding.*): SD1.5 and SD 2.x only")
+        raise RuntimeError(f"not a diffusers ControlNetModel state dict: {e.args[0]} is missing")
+    o = dict(block_out_channels=boc, cross_attention_dim=ctx, conditioning_embedding_out_channels=cc)
+    if lin:
+        o.update(use_linear_projection=True, attention_head_dim=tuple(c // 64 for c in boc))
+    return controlnet_config(None, o)
+
+
+def load_controlnet(path: str):
+    """-> (sd, cfg) of a diffusers ControlNetModel: a directory (config.json + diffusion_pytorch_model[.fp16].safetensors) or a
+    bare .safetensors with the same names.  Pickles (.ckpt / .bin / .pt / .pth) are refused, as for checkpoints."""
+    if os.path.isdir(path):
+        with open(os.path.join(path, "config.json")) as f:
+            cfg = _controlnet_cfg_from_json(json.load(f))
+        try:
+            sd = _load_safetensors_dir(path)
+        except FileNotFoundError:
+            if any(fn.endswith((".bin", ".ckpt", ".pt", ".pth")) for fn in os.listdir(path)):
+                raise RuntimeError(f"{path}: only .safetensors ControlNets are loaded; pickled weights (.bin / .ckpt) are refused")
+            raise
+    else:
+        if not path.endswith(".safetensors"):
+            raise RuntimeError(f"{path}: only .safetensors ControlNets are loaded; pickled weights (.ckpt / .bin) are refused")
+        from safetensors.torch import load_file
+        sd = {k: v.to(torch.float16) for k, v in load_file(path).items()}
+        cfg = _controlnet_cfg_from_tensors(sd)
+    if cfg.get("addition_time_embed_dim") or any(k.startswith("add_embedding.") for k in sd):
+        raise RuntimeError(f"{path}: SDXL ControlNets are not supported (text_time additional embedding): SD1.5 and SD 2.x only")
+    for name, shape, _ in controlnet_param_spec(cfg):
+        if name not in sd:
+            raise RuntimeError(f"controlnet/graph mismatch at '{name}': missing")
+        if tuple(sd[name].shape) != tuple(shape):
+            if sd[name].numel() != count_params([(name, shape, "")]):
+                raise RuntimeError(f"controlnet/graph mismatch at '{name}': expected {tuple(shape)}, got {tuple(sd[name].shape)}")
+            sd[name] = sd[name].reshape(shape)     # linear stored as 1x1 conv or vice versa
+    return sd, cfg
+
+
+CONTROLNET_MATCH_KEYS = ("block_out_channels", "layers_per_block", "cross_attention_dim", "attention_head_dim", "down_attn",
+                         "transformer_layers_per_block", "use_linear_projection")
+
+
+def check_controlnet_matches(ccfg: dict, ucfg: dict) -> None:
+    """Raise unless the ControlNet's encoder is the UNet's (its residuals are added to that UNet's skips)."""
+    ucfg = unet_config(ucfg)
+    if ucfg.get("addition_time_embed_dim") or ccfg.get("addition_time_embed_dim"):
+        raise RuntimeError("SDXL ControlNets are not supported: the UNet or the ControlNet has a text_time additional embedding")
+    def norm(v):
+        return tuple(v) if isinstance(v, (list, tuple)) else v
+    for k in CONTROLNET_MATCH_KEYS:
+        a, b = norm(ccfg.get(k)), norm(ucfg.get(k))
+        if k in ("attention_head_dim", "transformer_layers_per_block"):      # scalar and per-level spellings of one layout
+            n = len(ucfg["block_out_channels"])
+            a, b = (a if isinstance(a, tuple) else (a,) * n), (b if isinstance(b, tuple) else (b,) * n)
+        if a != b:
+            raise RuntimeError(f"ControlNet does not fit the loaded UNet: {k} is {a} in the ControlNet and {b} in the UNet")
+    cc = tuple(ccfg.get("conditioning_embedding_out_channels", ()))
+    if cc != CONTROLNET_COND_CHANNELS:
+        raise RuntimeError(f"ControlNet conditioning_embedding_out_channels is {cc}; the hint kernels are built for "
+                           f"{CONTROLNET_COND_CHANNELS}")
+
+
+# ---------------------------------------------------------------------------------------
 # real checkpoints (diffusers directory layout)
 # ---------------------------------------------------------------------------------------
 def _load_safetensors_dir(d: str) -> dict:
