@@ -62,6 +62,23 @@ bounded by U times the magnitude it produces (sampler_step_reference), never rel
 sqrt(alpha_t) ~ 0.07 at t = 999).  latents_pool8: L-term fp32 bin sums, (L + 1) U mean|x| before the fp16 store.
 vae_blend: 4 U (|a| + |b|).  vae_place_tile: the fp32 copy is exact, the u8 value is round-half-even(clamp(v/2 + 1/2) 255)
 except within 4 U 255 of a .5 tie, where either neighbour is accepted (and counted).
+
+ControlNet hint stack (hint_conv_u8 / hint_conv: one fp32 chain per output, no K split).  E_acc = acc_err(K, S) with K the
+number of non-zero K slots (54 for the u8 layer: 27 hi + 27 lo); the u8 layer's operand x = u8 / 255 is one fp32 division
+(U |x|) carried as fp16 hi + lo (2^-21 |x|), entering E through sum err |w|; the bias is the accumulator's first term (one
+rounding at the magnitude of the sum and of the bias); SiLU 1.1 E + 8 U |v|; then the fp16 store.  conv3x3_c4_res is
+conv3x3_c4 without the pre-transform (K = 72 slots: 36 hi + 36 lo) and with the fp16 residual added in fp32 BEFORE the one
+fp16 rounding: a conv rounded to fp16 first carries H |conv| more, which the bound does not hold.
+Re-noise: fl(fma(sb, n, fl(sa x))): two roundings, each at most U times a magnitude below |sa x| + |sb n| + their own
+error: 4 U (|sa x| + |sb n|) (tests/refine_reference.py).  Hand-over step: x^k is the `last` form of the sampler step
+(sampler_step_reference, bound E_k), lat its re-noise: 4 U (|nsa x^k| + |nsb n|) + |nsa| E_k.  With dup the copy written in
+front of ``lat`` (the other classifier-free-guidance half) must equal it bit for bit.
+
+What a contraction launch must not write (``HOOKED``).  Every tensor argument is copied before the launch; afterwards every
+argument that does not share storage with ``out`` is bit-identical, and so is every element of ``out``'s storage window
+outside the logical [batch, rows, columns] extent of the launch: the window runs from (ldo - columns) elements before the
+first output element (the gap columns in front of a column slice) to the end of the last row's pitch or of the tensor passed,
+whichever is further (rows past M, gap columns of the written rows).
 """
 from __future__ import annotations
 
@@ -668,15 +685,141 @@ def tiled_glue_reference(tiles, sample, H, W, overlap=0.25):
     return img, E + 1e-38
 
 
+
+# ---- ControlNet hint stack -------------------------------------------------------------------------------------------------
+HINT_U8_K = 54          # non-zero K slots of hint_conv_u8: 27 hi + 27 lo
+
+
+def hint_u8_input(img_u8, dev=None, lo=True):
+    """hint_conv_u8's operand: x = u8 / 255 (one fp32 division) carried as fp16 hi + lo -> (x [B, H, W, 3] fp64, its error).
+    lo=False: the error of a single fp16 (what the bound must NOT be: the CPU self-test)."""
+    x = img_u8.to(dev if dev is not None else img_u8.device, torch.float64) / 255.0
+    return x, ((2.0 ** -21 if lo else H) + U) * x.abs()
+
+
+def hint_layer_check(got, xin64, xerr, w, bias, B, Hh, Ww, stride, silu, K_eff, images=None):
+    """Worst |got - ref| / bound of one hint layer (hint_conv_u8 / hint_conv / the stack's last conv): xin64 [B, H, W, Cin] fp64
+    the layer's own stored input, xerr its operand error or None, got [B * Ho * Wo, Cout] (module docstring)."""
+    Ho, Wo = ((Hh + 1) // 2, (Ww + 1) // 2) if stride == 2 else (Hh, Ww)
+    worst = 0.0
+    b64 = bias.to(got.device, torch.float64) if bias is not None else None
+    for b in (range(B) if images is None else images):
+        xe = None if xerr is None else xerr[b]
+        for rows, Y, S, Eop in conv_bands(xin64[b], xe, w, stride=stride):
+            E = acc_err(K_eff, S)
+            if Eop is not None:
+                E = E + Eop + acc_err(K_eff, Eop)
+            v = Y
+            if b64 is not None:
+                v = Y + b64
+                E = E + U * (v.abs() + b64.abs())
+            if silu:
+                E = 1.1 * E + 8 * U * v.abs()
+                v = v * torch.sigmoid(v)
+            gr = slice(b * Ho * Wo + rows.start, b * Ho * Wo + rows.stop)
+            worst = max(worst, worst_ratio(got[gr], v, store_bound(v, E)))
+    return worst
+
+
+C4_RES_K = 72           # non-zero K slots of conv3x3_c4_res: 36 hi + 36 lo
+
+
+def conv_c4_res_check(got, lat, w, bias, res, B, Hh, Ww, images=None):
+    """conv3x3_c4_res: conv3x3 of the fp32 NCHW latents (hi + lo operand) + bias + res fp16 [B*H*W, Cout], the residual added
+    in fp32 before the single fp16 rounding."""
+    dev = got.device
+    z, ez = c4_input(lat[:B], None, None, 1.0)
+    worst = 0.0
+    for b in (range(B) if images is None else images):
+        for rows, Y, S, Eop in conv_bands(z[b].to(dev), ez[b].to(dev), w):
+            E = acc_err(C4_RES_K, S + Eop) + Eop
+            gr = slice(b * Hh * Ww + rows.start, b * Hh * Ww + rows.stop)
+            v, E = _epilogue(Y, S + Eop, E, bias=_f64(bias, dev), res=_f64(res[gr], dev))
+            worst = max(worst, worst_ratio(got[gr], v, store_bound(v, E)))
+    return worst
+
+
+# ---- multi-pass refinement: re-noise and the hand-over step ----------------------------------------------------------------
+def renoise_reference(x, n, sa, sb):
+    """lat = sa x + sb n from the fp32 operands (coefficients as the kernel receives them) -> (ref, bound)."""
+    sa, sb = float(np.float32(sa)), float(np.float32(sb))
+    X, N = x.to(torch.float64), n.to(torch.float64)
+    return sa * X + sb * N, 4 * U * ((sa * X).abs() + (sb * N).abs()) + 1e-38
+
+
+def _halves_ratio(lat, B, ref, bnd, dup):
+    """lat [>= B (2B with dup), 4, h, w] after the launch: the first B images against (ref, bnd); with dup images [B, 2B) must
+    equal them bit for bit (inf otherwise)."""
+    r = worst_ratio(lat[:B], ref, bnd)
+    if dup and not same_bits(lat[B:2 * B], lat[:B]):
+        return math.inf
+    return r
+
+
+def renoise_check(lat, x0, noise, sa, sb, B, dup):
+    ref, bnd = renoise_reference(x0[:B], noise[:B], sa, sb)
+    return _halves_ratio(lat, B, ref.to(lat.device), bnd.to(lat.device), dup)
+
+
+def handover_reference(m, lat, noise, coef6, nsa, nsb, *, m_u=None, guidance=1.0, pred="epsilon"):
+    """-> (x^k, its bound, the re-noised state, its bound): the `last` sampler step, then the re-noise of ITS result."""
+    xk, Ek = sampler_step_reference(m, lat, None, coef6, True, m_u=m_u, guidance=guidance, pred=pred)
+    ref, bnd = renoise_reference(xk, noise, nsa, nsb)
+    return xk, Ek, ref, bnd + abs(float(np.float32(nsa))) * Ek
+
+
+def handover_check(xk, state, front, m, lat0, noise, coef6, nsa, nsb, B, *, m_u=None, guidance=1.0, pred="epsilon"):
+    """xk / state [B, 4, h, w] after the launch, front: the copy in front of the state (dup) or None; lat0 the state before."""
+    rx, bx, rl, bl = handover_reference(m[:B], lat0[:B], noise[:B], coef6, nsa, nsb, m_u=None if m_u is None else m_u[:B],
+                                        guidance=guidance, pred=pred)
+    dev = xk.device
+    r = max(worst_ratio(xk[:B], rx.to(dev), bx.to(dev)), worst_ratio(state[:B], rl.to(dev), bl.to(dev)))
+    if front is not None and not same_bits(front[:B], state[:B]):
+        return math.inf
+    return r
+
+
+# ---- what a contraction launch must not write ------------------------------------------------------------------------------
+def storage_numel(t):
+    return t.untyped_storage().nbytes() // t.element_size()
+
+
+def out_window(out, rows, cols, ld, batch=1, stride_o=0):
+    """The window of ``out``'s storage a launch that writes [batch, rows, cols] at pitch ld (batch stride stride_o) from out's
+    first element is answerable for -> (start, length, keep): keep[i] True where storage element start + i is NOT part of the
+    logical output (module docstring)."""
+    off = out.storage_offset()
+    view_end = off + 1 + sum((n - 1) * st for n, st in zip(out.shape, out.stride())) if out.numel() else off
+    logical_end = off + (batch - 1) * stride_o + rows * ld
+    start = max(0, off - max(0, ld - cols))
+    end = min(storage_numel(out), max(view_end, logical_end))
+    keep = torch.ones(end - start, dtype=torch.bool, device=out.device)
+    keep.as_strided((batch, rows, cols), (stride_o, ld, 1), off - start).fill_(False)
+    return start, end - start, keep
+
+
+def window_of(t, start, length):
+    return t.as_strided((length,), (1,), start)
+
+
+def stray_writes(before, after, keep):
+    """number of elements of the window outside the logical output whose bits changed."""
+    it = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[before.element_size()]
+    return int(((before.view(it) != after.view(it)) & keep).sum())
+
+
 # ---- the hook ----------------------------------------------------------------------------------------------------------
 HOOKED = ("gemm", "gemm_ln", "mlp_geglu", "conv3x3", "conv3x3_gn", "conv3x3_smalln", "conv3x3_c4", "linear_rows",
-          "linear_smallm", "attention")
+          "linear_smallm", "attention", "hint_conv_u8", "hint_conv", "conv3x3_c4_res")
+WRITES = {"conv3x3_smalln": ("out", "out_f32")}      # HOOKED entry points that write more than ``out``
 # the other entry points of a pass -> the arguments each one writes (all others must come out of the launch unchanged);
 # "ws" is scratch of the standalone GroupNorm forms (partials + tables: any of it may change)
 CHECKED = {"groupnorm_tables_from_stats": ("ws",), "groupnorm": ("out", "ws"), "groupnorm_from_stats": ("out", "ws"),
            "layernorm": ("out",), "softmax_rows": ("x",), "transpose": ("out",), "embed_tokens": ("out",),
            "timestep_embedding": ("out",), "timestep_embedding_steps": ("out",), "scheduler_step": ("lat",),
-           "latents_pool8": ("out",), "vae_blend": ("b",), "vae_place_tile": ("out_u8", "out_f32")}
+           "latents_pool8": ("out",), "vae_blend": ("b",), "vae_place_tile": ("out_u8", "out_f32"),
+           "latents_renoise": ("lat",), "scheduler_step_handover": ("lat", "xk")}
+REFINE_ENTRIES = ("latents_renoise", "scheduler_step_handover")     # reached by refinement chains only (passes > 0)
 GN_ENTRIES = ("groupnorm_tables_from_stats", "groupnorm", "groupnorm_from_stats")
 
 
@@ -752,20 +895,60 @@ class Audit:
             if name in CHECKED:
                 return self._launch_checked(name, real, args, kw, A)
             out = A["out"]
-            keep = {}
-            for k, v in A.items():        # whatever the launch may overwrite: inputs sharing the output's storage
-                if torch.is_tensor(v) and k != "out" and v.untyped_storage().data_ptr() == out.untyped_storage().data_ptr():
-                    keep[k] = v.clone()
+            writes = WRITES.get(name, ("out",))
+            before = {k: v.clone() for k, v in A.items() if torch.is_tensor(v) and k not in writes}
+            shared = {k for k in before if A[k].untyped_storage().data_ptr() == out.untyped_storage().data_ptr()}
+            ext = self._out_extent(name, A)
+            w_start, w_len, w_keep = out_window(out, *ext)
+            w_before = window_of(out, w_start, w_len).clone()
             n0 = len(self.recs)
             r = real(*args, **kw)
             if out.is_cuda:
                 torch.cuda.current_stream().synchronize()
-            A.update(keep)
+            stray = []
+            for k, v in before.items():       # what the launch must not write: every operand outside the output's storage
+                if k not in shared and not same_bits(A[k], v):
+                    stray.append(f"operand {k} changed by the launch")
+            n_out = stray_writes(w_before, window_of(out, w_start, w_len), w_keep)
+            if n_out:
+                stray.append(f"operand out: {n_out} elements outside the logical [{ext[3]} x {ext[0]} x {ext[1]}] output (pitch "
+                             f"{ext[2]}) changed by the launch")
+            for k in shared:                  # inputs sharing the output's storage: the reference needs them as they were
+                A[k] = before[k]
             rec = self.recs[n0] if len(self.recs) > n0 else (None, None, None)
-            self._check(name, A, rec[0], rec[1] or {})
-            del keep, A
+            self._check(name, A, rec[0], rec[1] or {}, stray)
+            del before, w_before, w_keep, A
             return r
         return hooked
+
+    @staticmethod
+    def _out_extent(name, A):
+        """(rows, columns, pitch, batch, batch stride) of the logical output of a HOOKED launch, in elements of ``out``."""
+        out = A["out"]
+        if name == "gemm":
+            M = A["a"].shape[0] if A["M"] is None else A["M"]
+            N = A["w"].shape[0] if A["N"] is None else A["N"]
+            ldo = out.stride(-2) if A["ldo"] is None else A["ldo"]
+            return M, (N // 2 if A["epilogue"] == 1 else N), ldo, A["batch"], (A["strideO"] if A["batch"] > 1 else 0)
+        if name == "gemm_ln":
+            N = A["w"].shape[0]
+            return A["a"].shape[0], (N // 2 if A["epilogue"] == 1 else N), out.stride(0), 1, 0
+        if name == "mlp_geglu":
+            return A["x"].shape[0], A["x"].shape[1], out.stride(0), 1, 0
+        if name == "linear_rows":
+            return A["M"], A["N"], out.stride(0), 1, 0
+        if name == "linear_smallm":
+            return A["M"], A["N"], (out.stride(0) if A["ldo"] is None else A["ldo"]), 1, 0
+        if name == "attention":
+            return A["B"] * A["Sq"], A["heads"] * A["d"], A["ldo"], 1, 0
+        if name == "conv3x3_smalln":          # fp32 [B*H*W, Cout] (mode 0) or the u8 image: Cout values per pixel either way
+            return A["B"] * A["H"] * A["W"], A["Cout"], A["Cout"], 1, 0
+        if name in ("conv3x3_c4", "conv3x3_c4_res", "hint_conv_u8"):
+            return A["B"] * A["H"] * A["W"], A["Cout"], A["Cout"], 1, 0
+        if name == "hint_conv":
+            Ho, Wo = ((A["H"] + 1) // 2, (A["W"] + 1) // 2) if A["stride"] == 2 else (A["H"], A["W"])
+            return A["B"] * Ho * Wo, A["Cout"], A["Cout"], 1, 0
+        return A["B"] * Audit._stats_rows(name, A), A["Cout"], A["Cout"], 1, 0          # conv3x3, conv3x3_gn
 
     @staticmethod
     def _stats_tensor(name, A):
@@ -789,7 +972,7 @@ class Audit:
         self._note = {}
         ratio, kappa = getattr(self, "_ref_" + name)(B, A, r)
         self.checks.append(dict(op=name, key=None, entry=None, config=None, ratio=ratio, stats_ratio=None, kappa=kappa,
-                                **self._note))
+                                args=self._scalars(A), **self._note))
         return r
 
     def _config(self, key, meta):
@@ -804,16 +987,25 @@ class Audit:
             bm, bn, v = 0, 0, -1
         return entry, (key[0], bm, bn, splits, v)
 
-    def _check(self, name, A, key, meta):
+    @staticmethod
+    def _scalars(A):
+        """the non-tensor arguments of a launch (what the reach checks of the tests read)."""
+        return {k: (tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in A.items()
+                if isinstance(v, (int, float, bool, str, type(None), list, tuple))}
+
+    def _check(self, name, A, key, meta, stray=()):
         entry, cfg = self._config(key, meta)
         ratio, sratio = getattr(self, "_ref_" + name)(A)
+        if stray:                            # a write outside the launch's output fails the check, naming the operand
+            ratio = math.inf
         st = A.get("stats")
         if st is not None and st.P > 0:
             out = A["out"]
             rows_img = self._stats_rows(name, A)
             sratio = stats_check(st, out, out.shape[0] // rows_img)
         self.checks.append(dict(op=name, key=key, entry=(tuple(entry[:4]) if entry is not None else None), config=cfg,
-                                ratio=ratio, stats_ratio=sratio))
+                                ratio=ratio, stats_ratio=sratio, stray=list(stray), args=self._scalars(A),
+                                m_img=meta.get("m_img"), stats_P=(st.P if st is not None else None)))
 
     @staticmethod
     def _stats_rows(name, A):
@@ -918,6 +1110,22 @@ class Audit:
                 worst = max(worst, worst_ratio(A["out"][gr], v, store_bound(v, E)))
         return worst, None
 
+    def _ref_conv3x3_c4_res(self, A):
+        return conv_c4_res_check(A["out"], A["lat_f32"], A["w"], A["bias"], A["res"], A["B"], A["H"], A["W"],
+                                 images=_pick_images(A["B"], self.images)), None
+
+    def _ref_hint_conv_u8(self, A):
+        B, Hh, Ww = A["B"], A["H"], A["W"]
+        x, xerr = hint_u8_input(A["img_u8"].reshape(-1)[:B * Hh * Ww * 3].view(B, Hh, Ww, 3), A["out"].device)
+        return hint_layer_check(A["out"], x, xerr, A["w"], A["bias"], B, Hh, Ww, 1, A["silu"], HINT_U8_K,
+                                images=_pick_images(B, self.images)), None
+
+    def _ref_hint_conv(self, A):
+        B, Hh, Ww, Cin = A["B"], A["H"], A["W"], A["Cin"]
+        x = A["x"].reshape(-1)[:B * Hh * Ww * Cin].view(B, Hh, Ww, Cin).to(A["out"].device, torch.float64)
+        return hint_layer_check(A["out"], x, None, A["w"], A["bias"], B, Hh, Ww, A["stride"], A["silu"], 9 * Cin,
+                                images=_pick_images(B, self.images)), None
+
     def _ref_linear_rows(self, A):
         ref, bnd = linear_reference(A["x"], A["w"], A["M"], x_rows=A["x_rows"], bias=A["bias"], res=A["res"],
                                     res_rows=A["res_rows"], silu_in=A["silu_in"], silu_out=A["silu_out"])
@@ -1016,6 +1224,32 @@ class Audit:
                                           guidance=A["guidance"], pred=A["pred"])
         return worst_ratio(A["lat"], ref, bnd), None
 
+    def _ref_latents_renoise(self, B, A, r):
+        Bn, h, w, dup = A["B"], A["h"], A["w"], A["dup"]
+        n = (2 if dup else 1) * Bn * 4 * h * w
+        assert tail_same(A["lat"], B["lat"], n), "latents_renoise wrote past its images"
+        lat = A["lat"].reshape(-1)[:n].view(-1, 4, h, w)
+        x0 = B["x0"].reshape(-1)[:Bn * 4 * h * w].view(Bn, 4, h, w)
+        nz = B["noise"].reshape(-1)[:Bn * 4 * h * w].view(Bn, 4, h, w)
+        return renoise_check(lat, x0, nz, A["sqrt_a"], A["sqrt_b"], Bn, dup), None
+
+    @staticmethod
+    def _front_half(lat, n):
+        """the n elements in front of ``lat`` in its storage (the other classifier-free-guidance half of a [2B] state)."""
+        assert lat.is_contiguous() and lat.storage_offset() >= n, "hand-over with dup: no first half in front of the state"
+        return lat.as_strided((n,), (1,), lat.storage_offset() - n)
+
+    def _ref_scheduler_step_handover(self, B, A, r):
+        Bn, h, w, dup = A["B"], A["h"], A["w"], A["dup"]
+        n = Bn * 4 * h * w
+        assert tail_same(A["lat"], B["lat"], n) and tail_same(A["xk"], B["xk"], n), "hand-over step wrote past its images"
+        v = lambda t: t.reshape(-1)[:n].view(Bn, 4, h, w)
+        e = lambda t: None if t is None else t.reshape(-1)[:n].view(Bn, h, w, 4)
+        front = self._front_half(A["lat"], n).view(Bn, 4, h, w) if dup else None
+        return handover_check(v(A["xk"]), v(A["lat"]), front, e(B["eps"]), v(B["lat"]), v(B["noise"]), A["coef6"],
+                              A["next_sqrt_a"], A["next_sqrt_b"], Bn, m_u=e(B.get("eps_uncond")), guidance=A["guidance"],
+                              pred=A["pred"]), None
+
     def _ref_latents_pool8(self, B, A, r):
         Bn, h, w = A["B"], A["h"], A["w"]
         ref, bnd = pool8_reference(B["lat"].reshape(-1)[:Bn * 4 * h * w].view(Bn, 4, h, w))
@@ -1074,7 +1308,8 @@ def entry_table(checks):
 
 def failures(checks):
     """launches outside their bound, statistics outside theirs, or GroupNorm launches past the kappa tripwire."""
-    return [c for c in checks if not (c["ratio"] <= 1.0) or (c["stats_ratio"] is not None and not (c["stats_ratio"] <= 1.0))
+    return [c for c in checks if not (c["ratio"] <= 1.0) or c.get("stray")
+            or (c["stats_ratio"] is not None and not (c["stats_ratio"] <= 1.0))
             or (c.get("kappa") is not None and not (c["kappa"] <= KAPPA_TRIP))]
 
 

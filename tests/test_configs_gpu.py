@@ -226,14 +226,15 @@ def _audit_verdict(name, au, extra=""):
 
 
 def _audit_report(table):
-    from launch_audit import CHECKED, config_table, entry_table
+    from launch_audit import CHECKED, REFINE_ENTRIES, config_table, entry_table
     checks = [c for name in _AUDITED for c in _AUDITED[name][0]]
     per = entry_table(checks)
     for op in sorted(per):
         n, r, k = per[op]
         print(f"[audit] entry {op:>28}: {n:>5} launches checked, worst ratio {r:.3f}" + (f", worst kappa {k:.4g}" if k else ""))
     # every entry point the audit checks was reached by a real pass: a refactor that routes around ops.X fails here
-    missing = sorted(set(CHECKED) - set(per))
+    # (the two entry points of refinement chains are held to the same by tests/test_audit_ragged_gpu.py, whose passes run them)
+    missing = sorted(set(CHECKED) - set(REFINE_ENTRIES) - set(per))
     assert not missing, f"audited entry points no pass reached: {missing}"
     reached = set().union(*(v[1] for v in _AUDITED.values()))
     rows = config_table(checks)

@@ -47,27 +47,10 @@ def pe():
 
 # ---- hint stack: every layer against fp64 on the same fp16-rounded operands ---------------------------------------------
 def _layer_check(got, xin64, xerr, w, bias, B, H, W, stride, silu, K_eff):
-    """Worst |got - ref| / bound of one hint layer.  The bound is launch_audit's for a contraction: E_acc = C_ACC U sqrt(K) S from
-    the fp32 accumulation, the operand error through sum err |w|, one rounding for the bias, the SiLU's exp2 / rcp approximations
-    (8 U |v|, slope <= 1.1) and the fp16 store."""
+    """Worst |got - ref| / bound of one hint layer: launch_audit.hint_layer_check (the derivation lives there, with the audit's
+    other references: fp32 chain, operand error, bias, SiLU, the fp16 store)."""
     import launch_audit as la
-    Ho, Wo = ((H + 1) // 2, (W + 1) // 2) if stride == 2 else (H, W)
-    worst = 0.0
-    b64 = bias.to(got.device, torch.float64)
-    for b in range(B):
-        xe = None if xerr is None else xerr[b]
-        for rows, Y, S, Eop in la.conv_bands(xin64[b], xe, w, stride=stride):
-            E = la.acc_err(K_eff, S)
-            if Eop is not None:
-                E = E + Eop + la.acc_err(K_eff, Eop)
-            v = Y + b64
-            E = E + la.U * (v.abs() + b64.abs())
-            if silu:
-                E = 1.1 * E + 8 * la.U * v.abs()
-                v = v * torch.sigmoid(v)
-            gr = slice(b * Ho * Wo + rows.start, b * Ho * Wo + rows.stop)
-            worst = max(worst, la.worst_ratio(got[gr], v, la.store_bound(v, E)))
-    return worst
+    return la.hint_layer_check(got, xin64, xerr, w, bias, B, H, W, stride, silu, K_eff)
 
 
 def _hint_images(B, H, W, seed=0):
@@ -92,10 +75,9 @@ def test_hint_stack_layers_vs_fp64(nets, B, H, W):
     cn.embed_hint(hint, B, H, W, out)
     torch.cuda.synchronize()
     # layer 0: operand u8 / 255 carried as fp16 hi + lo (~22 bits) plus the fp32 division
-    x64 = hint.to(torch.float64) / 255.0
-    xerr = (2.0 ** -21 + la.U) * x64.abs()
+    x64, xerr = la.hint_u8_input(hint)
     got = cn.buf.get("hint0", B * H * W, COND[0])
-    worst = {0: _layer_check(got, x64, xerr, cn.w["hint.0.w"], cn.w["hint.0.b"], B, H, W, 1, True, 54)}
+    worst = {0: _layer_check(got, x64, xerr, cn.w["hint.0.w"], cn.w["hint.0.b"], B, H, W, 1, True, la.HINT_U8_K)}
     h, w = H, W
     x = got
     for i in range(6):

@@ -368,3 +368,248 @@ def test_tiled_glue_reference_matches_a_direct_restatement():
     assert (E < 1e-5).all()
     wrong = _glue_direct(tiles, len(ys), len(xs), 16, 48, left_first=True)
     assert la.worst_ratio(wrong, img, E) > 1.0, "left before above must not pass as the glue"
+
+
+# ---- odd geometry: cropped upsample targets, stride 2 on odd inputs, ragged key tiles ---------------------------------------
+def _im2col(img, stride=1, pad_mode="constant"):
+    """img [H, W, C] fp32 -> [Ho * Wo, 9 * C] (tap major, channel minor), padding 1."""
+    Hh, Ww, C = img.shape
+    xp = torch.nn.functional.pad(img.permute(2, 0, 1)[None], (1, 1, 1, 1), mode=pad_mode)[0].permute(1, 2, 0)
+    Ho, Wo = ((Hh + 1) // 2, (Ww + 1) // 2) if stride == 2 else (Hh, Ww)
+    parts = [xp[ky:ky + stride * (Ho - 1) + 1:stride, kx:kx + stride * (Wo - 1) + 1:stride] for ky in range(3) for kx in range(3)]
+    return torch.stack(parts, 2).reshape(Ho * Wo, 9 * C)
+
+
+def _conv_case(Hh, Ww, C=64, Cout=64, seed=30):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(Hh * Ww, C, generator=g).half()
+    w4 = torch.randn(Cout, C, 3, 3, generator=g) * (9 * C) ** -0.5
+    return x, w4
+
+
+def _up2(img):
+    return img.repeat_interleave(2, 0).repeat_interleave(2, 1)
+
+
+def test_odd_upsample_target_bound_rejects_an_ignored_crop_and_phase_weights_at_the_border():
+    """Upsample2D to an odd skip size: nearest 2x cropped to (2H-1, 2W-1), zero padding AFTER the crop, plain 3x3 weights.  A
+    conv of the full 2x image cropped afterwards, and the phase-packed form (which is that conv), differ in the last row and
+    column only -- and are rejected; crops in one direction only likewise."""
+    from sdlcm_amd.packing import pack_conv3x3, pack_conv3x3_up2
+    Hh, Ww, C = 5, 4, 64
+    x, w4 = _conv_case(Hh, Ww)
+    w = pack_conv3x3(w4).half()
+    img = x.float().reshape(Hh, Ww, C)
+    full = _kernel_like(_im2col(_up2(img)).half(), w).reshape(2 * Hh, 2 * Ww, -1)          # conv of the uncropped 2x image
+    wp = pack_conv3x3_up2(w4).half()
+    ph = torch.cat([t[1] for t in la.conv_bands(img.double(), None, wp, phases=True)]).half().reshape(2 * Hh, 2 * Ww, -1)
+    assert la.conv_check(ph.reshape(-1, 64), x, wp, 1, Hh, Ww, ups=2) <= 1.0              # the phase form is right for 2H x 2W
+    for Ho, Wo in ((2 * Hh - 1, 2 * Ww - 1), (2 * Hh - 1, 2 * Ww), (2 * Hh, 2 * Ww - 1)):
+        kw = dict(ups=1, out_hw=(Ho, Wo))
+        good = _kernel_like(_im2col(_up2(img)[:Ho, :Wo]).half(), w)
+        assert la.conv_check(good, x, w, 1, Hh, Ww, **kw) <= 1.0, (Ho, Wo)
+        late = full[:Ho, :Wo].reshape(Ho * Wo, -1)
+        assert la.conv_check(late, x, w, 1, Hh, Ww, **kw) > 1.0, ("crop ignored: full 2x conv cropped afterwards", Ho, Wo)
+        inner = (late.reshape(Ho, Wo, -1)[:2 * Hh - 2, :2 * Ww - 2] == good.reshape(Ho, Wo, -1)[:2 * Hh - 2, :2 * Ww - 2]).all()
+        assert inner, "the wrong form must differ in the last row / column only"
+        assert la.conv_check(ph[:Ho, :Wo].reshape(Ho * Wo, -1), x, w, 1, Hh, Ww, **kw) > 1.0, ("phase-packed weights at the border", Ho, Wo)
+
+
+def test_stride2_bound_on_an_odd_input_rejects_a_replicated_last_row():
+    from sdlcm_amd.packing import pack_conv3x3
+    for Hh, Ww in ((9, 7), (9, 8), (8, 7)):
+        x, w4 = _conv_case(Hh, Ww, seed=31)
+        w = pack_conv3x3(w4).half()
+        img = x.float().reshape(Hh, Ww, 64)
+        good = _kernel_like(_im2col(img, 2).half(), w)
+        assert good.shape[0] == ((Hh + 1) // 2) * ((Ww + 1) // 2)
+        assert la.conv_check(good, x, w, 1, Hh, Ww, stride=2) <= 1.0, (Hh, Ww)
+        if Hh % 2 or Ww % 2:        # the tap past an odd edge reads the zero row / column, not a copy of the last one
+            wrong = _kernel_like(_im2col(img, 2, "replicate").half(), w)
+            # only the far border may differ: keep the near border of the correct result
+            Ho, Wo = (Hh + 1) // 2, (Ww + 1) // 2
+            g3, w3 = good.reshape(Ho, Wo, -1), wrong.reshape(Ho, Wo, -1).clone()
+            w3[0], w3[:, 0] = g3[0], g3[:, 0]
+            if not Hh % 2:
+                w3[-1] = g3[-1]
+            if not Ww % 2:
+                w3[:, -1] = g3[:, -1]
+            assert la.conv_check(w3.reshape(Ho * Wo, -1), x, w, 1, Hh, Ww, stride=2) > 1.0, (Hh, Ww)
+
+
+def _attn_kernel_like(q, k, v, scale, extra_zero_key=False, drop_last=False):
+    """one head: fp32 logits of the fp16 operands, fp32 softmax sum, P rounded to fp16 for the PV product, fp16 store."""
+    K, V = k.float(), v.float()
+    if drop_last:
+        K, V = K[:-1], V[:-1]
+    if extra_zero_key:           # a padding row of a ragged last key tile that is not masked: logit 0, value 0
+        K, V = torch.cat([K, torch.zeros(1, K.shape[1])]), torch.cat([V, torch.zeros(1, V.shape[1])])
+    S = (q.float() @ K.T) * scale
+    p = torch.exp(S - S.max(1, keepdim=True).values)
+    return ((p.half().float() @ V) / p.sum(1, keepdim=True)).half()
+
+
+def test_attention_bound_rejects_a_padding_key_and_a_dropped_last_key():
+    """Sk = 63 (one ragged register-staged tile) and Sk = 825 (ragged last tile of the streaming kernel).  The logits of the
+    real keys sit near -5 (a zero padding key would carry weight), the last key near -1 with a value of its own (it carries
+    weight too); values are positive so that |o| is of the size of sum p |v|."""
+    d, Sq = 40, 16
+    scale = d ** -0.5
+    for Sk in (63, 825):
+        g = torch.Generator().manual_seed(32 + Sk)
+        q = (1.0 + 0.1 * torch.randn(Sq, d, generator=g)).half()
+        k = (-0.79 + 0.05 * torch.randn(Sk, d, generator=g))
+        k[-1] = -0.16
+        k = k.half()
+        v = (1.0 + 0.1 * torch.randn(Sk, d, generator=g))
+        v[-1] = 3.0
+        v = v.half()
+        chk = lambda got: la.attention_check(got, q, k, v, 1, 1, Sq, Sk, d, scale=scale)
+        assert chk(_attn_kernel_like(q, k, v, scale)) <= 1.0, Sk
+        assert chk(_attn_kernel_like(q, k, v, scale, extra_zero_key=True)) > 1.0, ("a zero padding key admitted", Sk)
+        assert chk(_attn_kernel_like(q, k, v, scale, drop_last=True)) > 1.0, ("the last real key dropped", Sk)
+
+
+# ---- ControlNet: hint stack, conv_in + hint embedding ----------------------------------------------------------------------
+def _hilo_chain(cols32, w16, bias, lo=True):
+    """fp32 chain bias + hi . w (+ lo . w): the operand enters the MFMA as fp16 hi + fp16 lo against the same weights."""
+    hi = cols32.half()
+    acc = (bias.float() if bias is not None else 0.0) + hi.float() @ w16.float().T
+    if lo:
+        acc = acc + (cols32 - hi.float()).half().float() @ w16.float().T
+    return acc
+
+
+def test_hint_u8_bound_rejects_an_input_carried_as_one_fp16():
+    from sdlcm_amd.packing import pack_conv3x3
+    g = torch.Generator().manual_seed(33)
+    B, Hh, Ww, Cout = 2, 24, 20, 16
+    img = torch.randint(0, 256, (B, Hh, Ww, 3), generator=g, dtype=torch.uint8)
+    img[0, :4, :4], img[0, -4:, -4:] = 0, 255
+    w = pack_conv3x3(torch.randn(Cout, 3, 3, 3, generator=g) * 27 ** -0.5).half()
+    bias = (0.01 * torch.randn(Cout, generator=g)).half()
+    x, xerr = la.hint_u8_input(img)
+
+    def run(lo):
+        x32 = img.float() / 255.0
+        acc = torch.cat([_hilo_chain(_im2col(x32[b]), w, bias, lo) for b in range(B)])
+        return (acc * torch.sigmoid(acc)).half()
+    chk = lambda got: la.hint_layer_check(got, x, xerr, w, bias, B, Hh, Ww, 1, True, la.HINT_U8_K)
+    assert chk(run(True)) <= 1.0
+    assert chk(run(False)) > 1.0, "u8 / 255 carried as a single fp16"
+    # hint_conv: a narrow fp16 layer at stride 2 on an odd input
+    xin = (torch.randn(B * 9 * 7, 16, generator=g)).half()
+    w2 = pack_conv3x3(torch.randn(32, 16, 3, 3, generator=g) * 144 ** -0.5).half()
+    b2 = (0.1 * torch.randn(32, generator=g)).half()
+    x3 = xin.float().reshape(B, 9, 7, 16)
+
+    def run2(mode, silu=True):
+        acc = torch.cat([b2.float() + _im2col(x3[b], 2, mode) @ w2.float().T for b in range(B)])
+        return (acc * torch.sigmoid(acc) if silu else acc).half()
+    chk2 = lambda got: la.hint_layer_check(got, x3.double(), None, w2, b2, B, 9, 7, 2, True, 144)
+    assert chk2(run2("constant")) <= 1.0
+    assert chk2(run2("replicate")) > 1.0 and chk2(run2("constant", silu=False)) > 1.0
+
+
+def test_conv_c4_res_bound_rejects_a_conv_rounded_before_the_residual():
+    """res ~ -conv: the sum is small, so the fp16 rounding of the conv alone (H |conv|) is far outside H |sum| + E."""
+    from sdlcm_amd.packing import pack_conv3x3
+    g = torch.Generator().manual_seed(34)
+    B, Hh, Ww, Cout = 2, 9, 7, 64
+    lat = torch.randn(2 * B, 4, Hh, Ww, generator=g) * 4.0               # [2B]: the launch reads the first B images
+    w = pack_conv3x3(torch.randn(Cout, 4, 3, 3, generator=g) * 0.3).half()
+    bias = (0.1 * torch.randn(Cout, generator=g)).half()
+    acc = torch.cat([_hilo_chain(_im2col(lat[b].permute(1, 2, 0)), w, bias) for b in range(B)])
+    res = (-acc + 0.01 * torch.randn(acc.shape, generator=g)).half()
+    chk = lambda got: la.conv_c4_res_check(got, lat, w, bias, res, B, Hh, Ww)
+    assert chk((acc + res.float()).half()) <= 1.0
+    assert chk((acc.half().float() + res.float()).half()) > 1.0, "conv rounded to fp16 before the residual"
+    assert chk(acc.half()) > 1.0, "residual dropped"
+
+
+# ---- refinement: re-noise and the hand-over step ----------------------------------------------------------------------------
+def test_renoise_and_handover_bounds_reject_an_unwritten_first_half():
+    from sdlcm_amd.scheduler import LCMSchedule
+    gen = torch.Generator().manual_seed(35)
+    B, h, w = 2, 9, 5
+    for pred in ("epsilon", "v_prediction"):
+        s = LCMSchedule(prediction_type=pred)
+        ts = s.timesteps(4, 0.5)
+        coef, last = s.step_coefficients(ts, 3)
+        assert last
+        nsa, nsb = s.renoise_coefficients(ts[0])
+        fsa, fsb = torch.tensor(nsa, dtype=torch.float32), torch.tensor(nsb, dtype=torch.float32)
+        m, mu = torch.randn(B, h, w, 4, generator=gen), torch.randn(B, h, w, 4, generator=gen)
+        x, n = torch.randn(B, 4, h, w, generator=gen) * 12, torch.randn(B, 4, h, w, generator=gen)
+        for cfg in (None, 5.0):
+            kw = dict(m_u=mu, g=cfg) if cfg else {}
+            rkw = dict(m_u=mu, guidance=cfg) if cfg else {}
+            xk = _step_kernel_like(m, x, None, coef, True, pred=pred, **kw)
+            state = fsa * xk + fsb * n
+            chk = lambda xk_, st_, front: la.handover_check(xk_, st_, front, m, x, n, coef, nsa, nsb, B, pred=pred, **rkw)
+            assert chk(xk, state, state.clone() if cfg else None) <= 1.0, (pred, cfg)
+            assert chk(xk, fsa * xk + fsb * n.flip(0), None) > 1.0, "re-noised with another image's noise"
+            assert chk(xk, fsb * xk + fsa * n, None) > 1.0, "re-noise coefficients swapped"
+            assert chk(state, state, None) > 1.0, "x^k holds the re-noised state"
+            if cfg:
+                assert chk(xk, state, x.clone()) > 1.0, "dup: the first half left unwritten"
+                front = state.clone()
+                front[1, 2, 3, 4] = torch.nextafter(front[1, 2, 3, 4], torch.tensor(1e9))
+                assert chk(xk, state, front) > 1.0, "dup: halves differ in one bit"
+        # latents_renoise: lat [2B] with dup
+        lat = torch.cat([fsa * x + fsb * n] * 2)
+        assert la.renoise_check(lat, x, n, nsa, nsb, B, True) <= 1.0 and la.renoise_check(lat[:B], x, n, nsa, nsb, B, False) <= 1.0
+        half = lat.clone()
+        half[B:] = -7.0
+        assert la.renoise_check(half, x, n, nsa, nsb, B, True) > 1.0, "dup: second copy unwritten"
+        assert la.renoise_check(torch.cat([fsa * x + fsa * n] * 2), x, n, nsa, nsb, B, True) > 1.0
+
+
+# ---- what a contraction launch must not write -------------------------------------------------------------------------------
+def _audited_fake_gemm(stray=None, touch_a=False):
+    """Audit's hook around an emulated lcm_gemm_f16 writing a column slice of a fused [M + 2, 3 N] buffer (the layout of the QKV
+    buffer / a skip concat with spare rows) -> the check it recorded.  stray: (row, column) of the buffer written on top."""
+    import inspect
+    from sdlcm_amd import ops
+    M, N, K = 70, 64, 128                       # a ragged last row tile
+    a, w, b = _operands(M, N, K, seed=36)
+    buf = torch.full((M + 2, 3 * N), 0.5, dtype=torch.float16)
+    out = buf[:, N:2 * N]
+    sig = inspect.signature(ops.gemm)
+
+    def fake(*args, **kw):
+        A = sig.bind(*args, **kw).arguments
+        o = A["out"]
+        o.as_strided((A["M"], A["N"]), (A["ldo"], 1), o.storage_offset()).copy_(_kernel_like(A["a"], A["w"], bias=A["bias"]))
+        if stray is not None:
+            buf[stray] = 1.0
+        if touch_a:
+            A["a"][3, 5] += 1
+        return o
+    fake.__signature__ = sig
+    au = la.Audit()
+    au.recs = []
+    au._wrap("gemm", fake)(a, w, out, bias=b, M=M, N=N, ldo=3 * N)
+    (c,) = au.checks
+    return c
+
+
+def test_hooked_launch_must_not_write_outside_its_logical_output():
+    M, N = 70, 64
+    c = _audited_fake_gemm()
+    assert c["ratio"] <= 1.0 and not c["stray"] and not la.failures([c])
+    for where, stray in (("one element past row M", (M, N + 3)), ("a gap column behind the slice", (2, 2 * N + 1)),
+                         ("a gap column in front of the slice", (5, N - 1)), ("the last spare row", (M + 1, 2 * N - 1))):
+        c = _audited_fake_gemm(stray)
+        assert c["ratio"] > 1.0 and len(c["stray"]) == 1 and "operand out" in c["stray"][0] and la.failures([c]), where
+    c = _audited_fake_gemm(touch_a=True)
+    assert c["ratio"] > 1.0 and "operand a" in c["stray"][0]
+    # the window arithmetic on its own: batched output with a batch stride, gap between the batch entries
+    buf = torch.zeros(2 * 40 + 8)
+    out = buf[4:]
+    start, n, keep = la.out_window(out, 3, 5, 8, batch=2, stride_o=40)
+    assert start == 1 and not keep[3:8].any() and keep[8:11].all() and not keep[3 + 40:8 + 40].any()
+    assert int((~keep).sum()) == 2 * 3 * 5
+    before = la.window_of(out, start, n).clone()
+    buf[4 + 40 + 2 * 8 + 5] = 1.0                # column 5 of the last row of batch entry 1: a gap column
+    assert la.stray_writes(before, la.window_of(out, start, n), keep) == 1

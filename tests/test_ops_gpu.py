@@ -1499,7 +1499,8 @@ def test_vae_tiled_decode_glue_fp64(H, W):
     vae.decode_plain = keep
     rgb = torch.zeros(1, H, W, 3, dtype=torch.uint8, device=DEV)
     img = torch.zeros(1, H, W, 3, dtype=torch.float32, device=DEV)
-    ops.set_workspace(torch.empty(16 << 20, dtype=torch.float32, device=DEV))
+    ws = torch.empty(16 << 20, dtype=torch.float32, device=DEV)   # held until it is unregistered: the library keeps a raw pointer,
+    ops.set_workspace(ws)                                          # and a dropped tensor's block is handed to the next allocation
     try:
         vae.decode(lat, 1, h, w, rgb, img_f32=img)
         torch.cuda.synchronize()
