@@ -97,10 +97,8 @@ class LoraStyle:
 
         def fold(name, d):
             """A delta of a weight that carries a folded LayerNorm (model.UNetHip._put_ln_fold): columns scaled by gamma,
-            plus the matching delta of the constant c = W beta + b.  -> (delta of gamma (*) W, delta of c) or (d, None)."""
+            plus the matching delta of the constant c = W beta + b.  -> (delta of gamma (*) W, delta of c)."""
             stem = name[:-2]
-            if (stem + ".lnw") not in unet.w:
-                return d, None
             return d * unet.w[stem + ".lnw"].float().cpu()[None, :], d @ unet.w[stem + ".lnb"].float().cpu()
 
         for mod, (down, up, alpha) in parsed.items():
@@ -115,7 +113,7 @@ class LoraStyle:
                 continue
             k, sub = re.match(r"^transformer_blocks\.(\d+)\.(.*)$", rest).groups()
             q, C = f"{p}.{k}", d.shape[0]
-            qs = getattr(unet, "qs", {}).get(q, 1.0)                         # to_q rows carry the softmax scale (model.Q_PRESCALE)
+            qs = unet.qs[q]                                                  # to_q rows carry the softmax scale (model._pack_transformer)
             if sub.startswith("attn1.to_") and sub[-1] in "qkv":
                 i = "qkv".index(sub[-1])
                 acc(q + ".qkv.w", (i * C, (i + 1) * C), *fold(q + ".qkv.w", d * qs if i == 0 else d))
@@ -146,7 +144,6 @@ class LoraStyle:
     @staticmethod
     def _conv_delta(unet, mod, down, up, alpha, acc):
         """LoCon / linear entries outside the transformer blocks, packed like the weight they modify (model.UNetHip)."""
-        from .model import UPS_PHASES
         r = down.shape[0]
         scale = alpha / r
         if mod.endswith(".time_emb_proj"):
@@ -164,7 +161,7 @@ class LoraStyle:
         if d4.shape[-1] != 3:
             raise ValueError(f"LoRA entry for {mod}: expected a 3x3 LoCon pair, got down {tuple(down.shape)}")
         name = mod + ".w"
-        packed = pack_conv3x3_up2(d4) if (".upsamplers." in mod and UPS_PHASES) else pack_conv3x3(d4)
+        packed = pack_conv3x3_up2(d4) if ".upsamplers." in mod else pack_conv3x3(d4)
         acc(name, (0, packed.shape[0]), packed)
         if (mod + ".w3") in unet.w:               # the upsampler's plain 3x3 copy (odd-sized targets) follows the style too
             p3 = pack_conv3x3(d4)

@@ -20,32 +20,19 @@ from .packing import pack_conv1x1, pack_conv3x3, pack_conv3x3_up2, pack_ff2_cols
 
 import os
 
-FUSED_GN_STATS = os.environ.get("LCM_FUSED_GN_STATS", "1") != "0"
-# Upsample2D (nearest-2x -> conv3x3) as four 2x2 phase convolutions on the low-resolution input (2.25x fewer MACs)
-UPS_PHASES = os.environ.get("LCM_UPS_PHASES", "1") != "0"
+# AutoencoderKL mid-block attention (one head, d = 512) as ONE fused flash kernel behind one q|k|v GEMM; "0" = the round-1
+# GEMM -> softmax -> transpose -> GEMM form with its B x S x S score matrix in HBM (kept for comparison)
+VAE_FLASH_ATTN = os.environ.get("LCM_VAE_FLASH_ATTN", "1") != "0"
 # GroupNorm-apply(+SiLU) inside the consuming conv's halo staging instead of its own pass over HBM -- where it pays:
 # the staged element is transformed once per n-tile of the conv, so few n-tiles (<= 4 with the 160-wide tile, <= 3 with
 # 128) and a tensor too large for the Infinity Cache, so that the separate pass really is HBM time (in situ the apply pass
 # reads what the producer just wrote: below ~64 MB it is served from MALL and fusing gains nothing; measured +1.5 % at
 # batch 8 and +0.2 % at batch 1 with the VAE's 512^2 / 256^2 levels fused; tools/gn_fuse_ab.py re-measures it per shape: profiles/r04_gn_fuse_ab.txt)
-# LayerNorm folded into the GEMM that consumes it (norm1 -> q|k|v, norm2 -> attn2.to_q, norm3 -> GEGLU proj): 192 launches
-# fewer per 512x512 4-step pass, no LayerNorm output in HBM (ops.gemm_ln / lcm_gemm_ln_f16)
-LN_FOLD = os.environ.get("LCM_LN_FOLD", "1") != "0"
-# conv_shortcut of a ResnetBlock2D on a forked side stream, concurrent with norm1 -> conv1 -> norm2 (see _Net.resnet).
-# OFF by default: measured on the same box, 512x512 4-step batch 1: 45.5 images/s with the 56 fork / join pairs per pass in
-# the captured graph against 47.6 without -- a cross-stream edge costs more here than the ~10 us GEMM it takes off the chain.
-FORK_SHORTCUT = os.environ.get("LCM_FORK_SHORTCUT", "0") != "0"
-FUSE_GN_CONV = os.environ.get("LCM_FUSE_GN_CONV", "1") != "0"
-# softmax scale (and log2 e) folded into the to_q weights of the UNet's attention layers (see _pack_transformer)
-Q_PRESCALE = os.environ.get("LCM_Q_PRESCALE", "1") != "0"
-# AutoencoderKL mid-block attention (one head, d = 512) as ONE fused flash kernel behind one q|k|v GEMM; "0" = the round-1
-# GEMM -> softmax -> transpose -> GEMM form with its B x S x S score matrix in HBM (kept for comparison)
-VAE_FLASH_ATTN = os.environ.get("LCM_VAE_FLASH_ATTN", "1") != "0"
 FUSE_GN_MIN_BYTES = int(os.environ.get("LCM_FUSE_GN_MIN_BYTES", str(64 << 20)))
 
 
 def _fuse_gn_into_conv(M, Cin, Cout):
-    if not (FUSE_GN_CONV and FUSED_GN_STATS) or Cin % 64 or Cout % 64:
+    if Cin % 64 or Cout % 64:
         return False
     ntiles = Cout // 160 if Cout % 160 == 0 else -(-Cout // 128)
     return M * Cin * 2 >= FUSE_GN_MIN_BYTES and ntiles <= (4 if Cout % 160 == 0 else 3)
@@ -79,7 +66,6 @@ class _Net:
         self.w = {}
         self.buf = _Buffers(device)
         self._stats = {}
-        self.side_stream = None       # set by the pipeline lane: a second stream for launches that fork off the main chain
 
     def _put(self, name, t, dtype=torch.float16):
         self.w[name] = _dev(t, self.device, dtype)
@@ -107,7 +93,7 @@ class _Net:
         (finalize + apply, no statistics pass over the data), else the standalone three-kernel form."""
         C = C1 + C2
         ws = self.gn_ws(B, HW, C)
-        if FUSED_GN_STATS and x_st is not None and x_st.P > 0 and (x2 is None or (x2_st is not None and x2_st.P > 0)):
+        if x_st is not None and x_st.P > 0 and (x2 is None or (x2_st is not None and x2_st.P > 0)):
             ops.groupnorm_from_stats(x, gamma, beta, out, B, HW, C1, x_st, ws, x2=x2, C2=C2, st2=x2_st, eps=eps, silu=silu)
         else:
             ops.groupnorm(x, gamma, beta, out, B, HW, C1, ws, x2=x2, C2=C2, eps=eps, silu=silu)
@@ -118,7 +104,7 @@ class _Net:
         applied inside the conv's staging pass (the normalised tensor never exists in memory); the choice depends on the layer's
         shape only, and both forms feed the conv the same fp16 values."""
         wt = self.w
-        if FUSED_GN_STATS and st is not None and st.P > 0 and ch % 64 == 0:
+        if st is not None and st.P > 0 and ch % 64 == 0:
             sc_t, sh_t = ops.groupnorm_tables_from_stats(wt[norm + ".g"], wt[norm + ".b"], B, H * W, ch, st, self.gn_ws(B, H * W, ch), eps=eps)
             ops.conv3x3_smalln(x, wt["conv_out.w"], out, B, H, W, ch, cout, bias=wt["conv_out.b"], mode=mode, out_f32=out_f32,
                                gn_scale=sc_t, gn_shift=sh_t, silu=True)
@@ -159,23 +145,12 @@ class _Net:
         HW, M, Cin = H * W, B * H * W, C1 + C2
         w = self.w
         have1 = x_st is not None and x_st.P > 0 and (x2 is None or (x2_st is not None and x2_st.P > 0))
-        # conv_shortcut (1x1 over the raw input) does not depend on norm1 -> conv1 -> norm2: with LCM_FORK_SHORTCUT=1 it forks
-        # onto the lane's side stream and joins before conv2 adds it as the residual (edges of the captured graph).  Measured
-        # slower than the serial chain (see FORK_SHORTCUT), so off by default.
-        sc, join = x, None
+        # conv_shortcut (1x1 over the raw input) stays on the main chain: forked onto a second stream, concurrent with
+        # norm1 -> conv1 -> norm2, it measured slower (a cross-stream edge costs more than the ~10 us GEMM)
+        sc = x
         if (p + ".sc.w") in w:
             sc = self.buf.get("shortcut", M, Cout)
-            side = self.side_stream if FORK_SHORTCUT else None
-            if side is not None:
-                fork = torch.cuda.Event()
-                fork.record()
-                with torch.cuda.stream(side):
-                    side.wait_event(fork)
-                    ops.gemm(x, w[p + ".sc.w"], sc, bias=w[p + ".sc.b"], a2=x2, img_rows=HW)
-                    join = torch.cuda.Event()
-                    join.record()
-            else:
-                ops.gemm(x, w[p + ".sc.w"], sc, bias=w[p + ".sc.b"], a2=x2, img_rows=HW)
+            ops.gemm(x, w[p + ".sc.w"], sc, bias=w[p + ".sc.b"], a2=x2, img_rows=HW)
         h1 = self.buf.get("conv1", M, Cout)
         h1_st = self.stats("conv1", M, Cout, HW)
         if have1 and C1 % 64 == 0 and C2 % 64 == 0 and _fuse_gn_into_conv(M, Cin, Cout):
@@ -192,15 +167,11 @@ class _Net:
         if h1_st.P > 0 and _fuse_gn_into_conv(M, Cout, Cout):
             sc_t, sh_t = ops.groupnorm_tables_from_stats(w[p + ".norm2.g"], w[p + ".norm2.b"], B, HW, Cout, h1_st,
                                                          self.gn_ws(B, HW, Cout), eps=eps)
-            if join is not None:
-                torch.cuda.current_stream().wait_event(join)
             ops.conv3x3_gn(h1, w[p + ".conv2.w"], out, B, H, W, Cout, Cout, gn_scale=sc_t, gn_shift=sh_t, silu=True,
                            bias=w[p + ".conv2.b"], res=sc, stats=out_st)
         else:
             hn2 = self.buf.get("gn", M, Cout)
             self.norm(h1, w[p + ".norm2.g"], w[p + ".norm2.b"], hn2, B, HW, Cout, x_st=h1_st, eps=eps)
-            if join is not None:
-                torch.cuda.current_stream().wait_event(join)
             ops.conv3x3(hn2, w[p + ".conv2.w"], out, B, H, W, Cout, Cout, bias=w[p + ".conv2.b"], res=sc, stats=out_st)
         return out, out_st
 
@@ -288,29 +259,20 @@ class _UNetEncoder(_Net):
         self._put(p + ".proj_out.b", sd[p + ".proj_out.bias"])
         for k in range(depth):
             t, q = f"{p}.transformer_blocks.{k}", f"{p}.{k}"
-            for n in ("norm1", "norm2", "norm3"):
-                self._put(f"{q}.{n}.g", sd[f"{t}.{n}.weight"])
-                self._put(f"{q}.{n}.b", sd[f"{t}.{n}.bias"])
             wqkv = torch.cat([sd[f"{t}.attn1.to_{n}.weight"] for n in "qkv"], 0).float()
             wq2, wff, bff = sd[f"{t}.attn2.to_q.weight"].float(), sd[f"{t}.ff.net.0.proj.weight"], sd[f"{t}.ff.net.0.proj.bias"]
-            if Q_PRESCALE:
-                # softmax scale d^-0.5 and the exp2 conversion log2(e), multiplied into the (bias-free) to_q rows in fp32 before
-                # the one fp16 rounding of the weight: the attention kernels then take q as it comes out of the projection
-                # (no second fp16 rounding of a scaled copy, no per-element multiply); lora.LoraStyle scales its to_q deltas alike
-                C = wq2.shape[0]
-                self.qs[q] = qs = (C // heads) ** -0.5 * 1.4426950408889634
-                wqkv[:C] *= qs
-                wq2 = wq2 * qs
-            if LN_FOLD:
-                self._put_ln_fold(q + ".qkv", wqkv, None, sd[f"{t}.norm1.weight"], sd[f"{t}.norm1.bias"])
-                self._put_ln_fold(q + ".q2", wq2, None, sd[f"{t}.norm2.weight"], sd[f"{t}.norm2.bias"])
-                self._put_ln_fold(q + ".ff1", wff, bff, sd[f"{t}.norm3.weight"], sd[f"{t}.norm3.bias"], geglu=True)
-            else:
-                self._put(q + ".qkv.w", wqkv)
-                self._put(q + ".q2.w", wq2)
-                wp, bp = pack_geglu(wff, bff)
-                self._put(q + ".ff1.w", wp)
-                self._put(q + ".ff1.b", bp)
+            # softmax scale d^-0.5 and the exp2 conversion log2(e), multiplied into the (bias-free) to_q rows in fp32 before
+            # the one fp16 rounding of the weight: the attention kernels then take q as it comes out of the projection
+            # (no second fp16 rounding of a scaled copy, no per-element multiply); lora.LoraStyle scales its to_q deltas alike
+            C = wq2.shape[0]
+            self.qs[q] = qs = (C // heads) ** -0.5 * 1.4426950408889634
+            wqkv[:C] *= qs
+            wq2 = wq2 * qs
+            # LayerNorm folded into the GEMM that consumes it (norm1 -> q|k|v, norm2 -> attn2.to_q, norm3 -> GEGLU proj): 192
+            # launches fewer per 512x512 4-step pass, no LayerNorm output in HBM (ops.gemm_ln / lcm_gemm_ln_f16)
+            self._put_ln_fold(q + ".qkv", wqkv, None, sd[f"{t}.norm1.weight"], sd[f"{t}.norm1.bias"])
+            self._put_ln_fold(q + ".q2", wq2, None, sd[f"{t}.norm2.weight"], sd[f"{t}.norm2.bias"])
+            self._put_ln_fold(q + ".ff1", wff, bff, sd[f"{t}.norm3.weight"], sd[f"{t}.norm3.bias"], geglu=True)
             self._put(q + ".o1.w", sd[f"{t}.attn1.to_out.0.weight"])
             self._put(q + ".o1.b", sd[f"{t}.attn1.to_out.0.bias"])
             self._put(q + ".o2.w", sd[f"{t}.attn2.to_out.0.weight"])
@@ -401,40 +363,27 @@ class _UNetEncoder(_Net):
         self.norm(x, w[p + ".norm.g"], w[p + ".norm.b"], hn, B, HW, C, x_st=x_st, eps=1e-6, silu=False)
         h = self.buf.get("tf_h", M, C)
         ops.gemm(hn, w[p + ".proj_in.w"], h, bias=w[p + ".proj_in.b"], img_rows=HW)
-        n = self.buf.get("tf_ln", M, C)
         qkv = self.buf.get("tf_qkv", M, 3 * C)
         a = self.buf.get("tf_attn", M, C)
         q2 = self.buf.get("tf_q2", M, C)
         ff = self.buf.get("tf_ff", M, 4 * C)
         for k in range(depth):
             q = f"{p}.{k}"
-            if LN_FOLD:
-                ops.gemm_ln(h, w[q + ".qkv.w"], w[q + ".qkv.g"], w[q + ".qkv.c"], qkv, img_rows=HW)
-            else:
-                ops.layernorm(h, w[q + ".norm1.g"], w[q + ".norm1.b"], n, M, C)
-                ops.gemm(n, w[q + ".qkv.w"], qkv, img_rows=HW)
+            ops.gemm_ln(h, w[q + ".qkv.w"], w[q + ".qkv.g"], w[q + ".qkv.c"], qkv, img_rows=HW)
             ops.attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], a, B, heads, HW, HW, d, ldq=3 * C, ldk=3 * C,
-                          ldv=3 * C, ldo=C, scale=0.0 if Q_PRESCALE else None)
+                          ldv=3 * C, ldo=C, scale=0.0)          # scale 0: q carries it (see _pack_transformer)
             ops.gemm(a, w[q + ".o1.w"], h, bias=w[q + ".o1.b"], res=h, img_rows=HW)
-            if LN_FOLD:
-                ops.gemm_ln(h, w[q + ".q2.w"], w[q + ".q2.g"], w[q + ".q2.c"], q2, img_rows=HW)
-            else:
-                ops.layernorm(h, w[q + ".norm2.g"], w[q + ".norm2.b"], n, M, C)
-                ops.gemm(n, w[q + ".q2.w"], q2, img_rows=HW)
+            ops.gemm_ln(h, w[q + ".q2.w"], w[q + ".q2.g"], w[q + ".q2.c"], q2, img_rows=HW)
             off, _ = self.kv_off[q]
             ops.attention(q2, kv_all[:, off:off + C], kv_all[:, off + C:off + 2 * C], a, B, heads, HW, TEXT_SEQ_LEN, d,
-                          ldq=C, ldk=self.kv_total, ldv=self.kv_total, ldo=C, scale=0.0 if Q_PRESCALE else None)
+                          ldq=C, ldk=self.kv_total, ldv=self.kv_total, ldo=C, scale=0.0)
             ops.gemm(a, w[q + ".o2.w"], h, bias=w[q + ".o2.b"], res=h, img_rows=HW)
-            if LN_FOLD and ops.mlp_fused_applies(M, C, HW):
+            if ops.mlp_fused_applies(M, C, HW):
                 # norm3 -> ff.net.0 -> GEGLU -> ff.net.2 -> + h as ONE kernel: the [M, 4C] intermediate stays on the CU.  A launch
                 # parameter like the tile shape: chosen from the total row count, bit-identical to the two launches below
                 ops.mlp_geglu(h, w[q + ".ff1.w"], w[q + ".ff1.g"], w[q + ".ff1.c"], w[q + ".ff2.w"], w[q + ".ff2.b"], h, img_rows=HW)
                 continue
-            if LN_FOLD:
-                ops.gemm_ln(h, w[q + ".ff1.w"], w[q + ".ff1.g"], w[q + ".ff1.c"], ff, epilogue=1, img_rows=HW)
-            else:
-                ops.layernorm(h, w[q + ".norm3.g"], w[q + ".norm3.b"], n, M, C)
-                ops.gemm(n, w[q + ".ff1.w"], ff, bias=w[q + ".ff1.b"], epilogue=1, img_rows=HW)
+            ops.gemm_ln(h, w[q + ".ff1.w"], w[q + ".ff1.g"], w[q + ".ff1.c"], ff, epilogue=1, img_rows=HW)
             ops.gemm(ff, w[q + ".ff2.w"], h, bias=w[q + ".ff2.b"], res=h, img_rows=HW)
         out = self.buf.get(out_role, M, C)
         out_st = self.stats(out_role, M, C, HW)
@@ -506,9 +455,10 @@ class UNetHip(_UNetEncoder):
                     self._pack_transformer(sd, f"up_blocks.{i}.attentions.{j}", kv_list, depth_at(cfg, nb - 1 - i), heads_at(cfg, nb - 1 - i))
             if i < nb - 1:
                 p = f"up_blocks.{i}.upsamplers.0.conv"
-                self._put(p + ".w", (pack_conv3x3_up2 if UPS_PHASES else pack_conv3x3)(sd[p + ".weight"]))
-                if UPS_PHASES:       # plain 3x3 layout too: upsampling to an odd-sized skip cannot use the pre-summed phase weights
-                    self._put(p + ".w3", pack_conv3x3(sd[p + ".weight"]))
+                # Upsample2D (nearest-2x -> conv3x3) as four 2x2 phase convolutions on the low-resolution input (2.25x fewer MACs)
+                self._put(p + ".w", pack_conv3x3_up2(sd[p + ".weight"]))
+                # plain 3x3 layout too: upsampling to an odd-sized skip cannot use the pre-summed phase weights
+                self._put(p + ".w3", pack_conv3x3(sd[p + ".weight"]))
                 self._put(p + ".b", sd[p + ".bias"])
         self._put("conv_norm_out.g", sd["conv_norm_out.weight"])
         self._put("conv_norm_out.b", sd["conv_norm_out.bias"])
@@ -580,10 +530,9 @@ class UNetHip(_UNetEncoder):
                 y = self.buf.get("ups", B * Ho * Wo, ch)
                 st = self.stats("ups", B * Ho * Wo, ch, Ho * Wo)
                 if (Ho, Wo) == (2 * H, 2 * W):
-                    ops.conv3x3(x, wt[p + ".w"], y, B, H, W, ch, ch, bias=wt[p + ".b"], ups=2 if UPS_PHASES else 1, stats=st)
+                    ops.conv3x3(x, wt[p + ".w"], y, B, H, W, ch, ch, bias=wt[p + ".b"], ups=2, stats=st)
                 else:                # odd target: the conv pads the CROPPED upsampled image with zeros -> loader-fused form
-                    ops.conv3x3(x, wt[p + (".w3" if UPS_PHASES else ".w")], y, B, H, W, ch, ch, bias=wt[p + ".b"], ups=1,
-                                stats=st, out_hw=(Ho, Wo))
+                    ops.conv3x3(x, wt[p + ".w3"], y, B, H, W, ch, ch, bias=wt[p + ".b"], ups=1, stats=st, out_hw=(Ho, Wo))
                 H, W, x = Ho, Wo, y
                 tap(f"up_blocks.{i}.upsamplers.0", x, ch, H, W)
         hn = self.buf.get("gn", B * H * W, ch)
@@ -735,7 +684,7 @@ class VAEDecoderHip(_Net):
                 self._pack_resnet(sd, f"decoder.up_blocks.{i}.resnets.{j}")
             if i < nb - 1:
                 p = f"decoder.up_blocks.{i}.upsamplers.0.conv"
-                self._put(p + ".w", (pack_conv3x3_up2 if UPS_PHASES else pack_conv3x3)(sd[p + ".weight"]))
+                self._put(p + ".w", pack_conv3x3_up2(sd[p + ".weight"]))
                 self._put(p + ".b", sd[p + ".bias"])
         self._put("norm_out.g", sd["decoder.conv_norm_out.weight"])
         self._put("norm_out.b", sd["decoder.conv_norm_out.bias"])
@@ -855,7 +804,7 @@ class VAEDecoderHip(_Net):
                 p = f"decoder.up_blocks.{i}.upsamplers.0.conv"
                 y = self.buf.get("ups", B * 4 * H * W, ch)
                 st = self.stats("ups", B * 4 * H * W, ch, 4 * H * W)
-                ops.conv3x3(x, wt[p + ".w"], y, B, H, W, ch, ch, bias=wt[p + ".b"], ups=2 if UPS_PHASES else 1, stats=st)
+                ops.conv3x3(x, wt[p + ".w"], y, B, H, W, ch, ch, bias=wt[p + ".b"], ups=2, stats=st)
                 H, W, x = 2 * H, 2 * W, y
                 tap(f"decoder.up_blocks.{i}.upsamplers.0", x, ch, H, W)
         hn = self.buf.get("gn", B * H * W, ch)

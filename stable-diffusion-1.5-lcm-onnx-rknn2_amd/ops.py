@@ -63,7 +63,7 @@ class _Timed:
     """Launch-order record of the algorithmic work of each MFMA launch; durations come from the library's own
     event brackets (lcm_profile_begin / lcm_profile_end), matched 1:1 by launch order."""
 
-    def __init__(self, kind, tile, flops, bytes_):
+    def __init__(self, kind, flops, bytes_):
         self.rec = None
         if _profile_list() is not None:
             self.rec = dict(kind=kind, flops=float(flops), bytes=float(bytes_))
@@ -99,11 +99,6 @@ def canonical_splits(kind, m_img, N, K, aux=1, ph=0):
     if n < 0:
         _lib.check(n, "lcm_canonical_splits")
     return n
-
-
-def tile_config(M, N, batch=1):
-    c = _lib.load().lcm_gemm_tile_config(int(M), int(N), int(batch))
-    return f"{c // 1000}x{c % 1000}"
 
 
 class Stats:
@@ -153,8 +148,7 @@ def gemm(a, w, out, *, bias=None, res=None, rowadd=None, rows_per_batch=0, a2=No
         RECORD.append(((0, M, N, K, batch), dict(halo=False, geglu=(epilogue == 1), m_img=(img_rows if img_rows and M % img_rows == 0 else M),
                                                  splittable=(epilogue == 0 and batch == 1 and not (strideA or strideW or strideO))),
                        lambda: gemm(a, w, out, **kw)))
-    with _Timed("gemm", tile_config(M, N, batch) if _profile_list() is not None else "", 2.0 * M * N * K * batch,
-                2.0 * batch * (M * K + N * K + M * N)):
+    with _Timed("gemm", 2.0 * M * N * K * batch, 2.0 * batch * (M * K + N * K + M * N)):
         rc = L.lcm_gemm_f16(_p(a), lda, _p(a2), a2.stride(0) if a2 is not None else 0, K1, _p(w), _p(bias), _p(rowadd),
                             rowadd.stride(0) if rowadd is not None else 0, rows_per_batch,
                             _p(res), res.stride(0) if res is not None else 0, _p(out), ldo,
@@ -177,7 +171,7 @@ def gemm_ln(a, w, ln_g, ln_c, out, *, eps=1e-5, epilogue=0, img_rows=0):
         RECORD.append(((0, M, N, K, 1), dict(halo=False, geglu=(epilogue == 1), m_img=(img_rows if img_rows and M % img_rows == 0 else M),
                                              splittable=False),
                        lambda: gemm_ln(a, w, ln_g, ln_c, out, eps=eps, epilogue=epilogue, img_rows=img_rows)))
-    with _Timed("gemm", "", 2.0 * M * N * K, 2.0 * (M * K + N * K + M * N)):
+    with _Timed("gemm", 2.0 * M * N * K, 2.0 * (M * K + N * K + M * N)):
         rc = L.lcm_gemm_ln_f16(_p(a), a.stride(0), _p(w), _p(ln_g), _p(ln_c), float(eps), _p(out), out.stride(0), M, N, K,
                                int(epilogue), int(img_rows), _stream())
     _lib.check(rc, "lcm_gemm_ln_f16")
@@ -208,7 +202,7 @@ def mlp_geglu(x, w1, ln_g, ln_c, w2, b2, out, *, eps=1e-5, img_rows=0):
     RECORD = _record_list()
     if RECORD is not None:          # nothing to tune (no tile / variant choice): recorded for the replay legs only
         RECORD.append((None, None, lambda: mlp_geglu(x, w1, ln_g, ln_c, w2, b2, out, eps=eps, img_rows=img_rows)))
-    with _Timed("mlp", "fused", 2.0 * M * (2 * F) * Cc + 2.0 * M * Cc * F, 2.0 * (2 * M * Cc + 2 * F * Cc + Cc * F)):
+    with _Timed("mlp", 2.0 * M * (2 * F) * Cc + 2.0 * M * Cc * F, 2.0 * (2 * M * Cc + 2 * F * Cc + Cc * F)):
         rc = L.lcm_mlp_geglu_f16(_p(x), x.stride(0), _p(w1), _p(ln_g), _p(ln_c), float(eps), _p(w2), _p(b2), _p(out),
                                  out.stride(0), M, Cc, int(img_rows), _stream())
     _lib.check(rc, "lcm_mlp_geglu_f16")
@@ -242,8 +236,7 @@ def conv3x3(x, w, out, B, H, W, Cin, Cout, *, bias=None, rowadd=None, res=None, 
         key = (1, Mo, Cout, 9 * Cin, 1) if stride == 2 else (2, Mo, Cout, taps * Cin, (Wo << 1))
         RECORD.append((key, dict(halo=stride == 1, W=(W if ups == 2 else Wo), phases=4 if ups == 2 else 1, m_img=Mo // B, splittable=True),
                        lambda: conv3x3(x, w, out, B, H, W, Cin, Cout, **kw)))
-    with _Timed("conv3x3", tile_config(Mo, Cout) if _profile_list() is not None else "", 2.0 * Mo * Cout * taps * Cin,
-                2.0 * (B * H * W * Cin + 9 * Cin * Cout + Mo * Cout)):
+    with _Timed("conv3x3", 2.0 * Mo * Cout * taps * Cin, 2.0 * (B * H * W * Cin + 9 * Cin * Cout + Mo * Cout)):
         rc = L.lcm_conv3x3_f16(_p(x), _p(w), _p(bias), _p(rowadd), rowadd.stride(0) if rowadd is not None else 0,
                                _p(res), _p(out), B, H, W, Cin, Cout, stride, flags, sbuf, sbytes,
                                C.byref(sp) if sp is not None else None, _stream())
@@ -267,7 +260,7 @@ def conv3x3_gn(x, w, out, B, H, W, C1, Cout, *, x2=None, C2=0, gn_scale=None, gn
                   stats=stats)
         RECORD.append(((2, Mo, Cout, 9 * Cin, (Wo << 1) | (1 if gn_scale is not None else 0)),
                        dict(halo=True, W=Wo, m_img=Mo // B, splittable=True), lambda: conv3x3_gn(x, w, out, B, H, W, C1, Cout, **kw)))
-    with _Timed("conv3x3", "halo", 2.0 * Mo * Cout * 9 * Cin, 2.0 * (B * H * W * Cin + 9 * Cin * Cout + Mo * Cout)):
+    with _Timed("conv3x3", 2.0 * Mo * Cout * 9 * Cin, 2.0 * (B * H * W * Cin + 9 * Cin * Cout + Mo * Cout)):
         rc = L.lcm_conv3x3_gn_f16(_p(x), C1, _p(x2), C2 if x2 is not None else 0, _p(gn_scale), _p(gn_shift),
                                   1 if silu else 0, _p(w), _p(bias), _p(rowadd),
                                   rowadd.stride(0) if rowadd is not None else 0, _p(res), _p(out), B, H, W, Cout, ups,
@@ -392,14 +385,14 @@ def embed_tokens(ids, tok_emb, pos_emb, out, B, S, D):
 
 
 def attention(q, k, v, out, B, heads, Sq, Sk, d, *, ldq, ldk, ldv, ldo, scale=None, causal=False):
-    """scale None: d^-0.5.  scale 0: q already carries scale * log2(e) (folded into the projection that made it, model.Q_PRESCALE)."""
+    """scale None: d^-0.5.  scale 0: q already carries scale * log2(e) (folded into the to_q weights, model._pack_transformer)."""
     L = _lib.load()
     scale = d ** -0.5 if scale is None else scale
     RECORD = _record_list()
     if RECORD is not None:
         RECORD.append((None, None, lambda: attention(q, k, v, out, B, heads, Sq, Sk, d, ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo,
                                                      scale=scale, causal=causal)))
-    with _Timed("attention", f"d{d}", 4.0 * B * heads * Sq * Sk * d, 2.0 * B * heads * d * (2 * Sq + 2 * Sk)):
+    with _Timed("attention", 4.0 * B * heads * Sq * Sk * d, 2.0 * B * heads * d * (2 * Sq + 2 * Sk)):
         rc = L.lcm_attention_f16(_p(q), ldq, _p(k), ldk, _p(v), ldv, _p(out), ldo, B, heads, Sq, Sk, d, float(scale),
                                  1 if causal else 0, _stream())
     _lib.check(rc, "lcm_attention_f16")

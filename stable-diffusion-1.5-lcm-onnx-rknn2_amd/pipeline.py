@@ -72,10 +72,10 @@ def _default_workspace(device):
     return t
 
 
-def _new_workspace(device, mb=None):
+def _new_workspace(device):
     # sized for a batch of 8 at 768x768 (472 MB) / SDXL 1024x1024 (fp32 [splits][M][N] of the largest split layer); a launch
     # that needs more fails loudly (a silently smaller split factor would change the numbers)
-    return torch.empty(int(mb if mb is not None else os.environ.get("LCM_SPLITK_WS_MB", "1024")) << 18, dtype=torch.float32, device=device)
+    return torch.empty(int(os.environ.get("LCM_SPLITK_WS_MB", "1024")) << 18, dtype=torch.float32, device=device)
 
 
 class _Lane:
@@ -95,20 +95,13 @@ class _Lane:
         # bake its pointer in) and is unregistered by LcmHipPipeline.close().
         self.splitk_ws = _new_workspace(pipe.device)
         ops.set_stream_workspace(self.stream, self.splitk_ws)
-        # side stream: launches that fork off the main chain inside one pass (the resnets' conv_shortcut GEMMs), with a
-        # split-K workspace of its own -- they run concurrently with the main stream's split layers
-        self.side = ops.acquire_stream(pipe.device)
-        self.side_ws = _new_workspace(pipe.device, mb=256)
-        ops.set_stream_workspace(self.side, self.side_ws)
-        self.unet.side_stream = self.side
-        self.vae.side_stream = self.side
         self.controlnet = None        # this lane's executor of the pipeline's ControlNet (LcmHipPipeline.lane_controlnet)
         self._controlnet_of = None
 
 
 class _Plan:
     """Buffers + captured graph for one (B, h, w, steps, cfg) key.  refine = (strength, passes to run, starts from cached
-    latents) makes it the plan of a refinement chain (LcmHipPipeline._enqueue_refine); None: the plain sampler."""
+    latents) makes it the plan of a refinement chain; None: the plain sampler (LcmHipPipeline._enqueue runs both)."""
 
     def __init__(self, pipe, B, h, w, steps, do_cfg, lane=None, refine=None, control=None):
         # Every zero-fill below must be ordered before the first use on the lane's (non-blocking) stream: allocate
@@ -222,18 +215,31 @@ class LcmHipPipeline:
             raise LcmHipError("this request carries a ControlNet hint but no ControlNet is loaded (set_controlnet)")
         if L._controlnet_of is not self.controlnet:
             L.controlnet = self.controlnet if L.index == 0 else self.controlnet.view()
-            L.controlnet.side_stream = L.side
             L._controlnet_of = self.controlnet
         return L.controlnet
 
     def _enqueue(self, P: _Plan, guidance: float, want_float=False, taps=None):
-        """Enqueue the whole sampler on the current stream (this is what gets captured)."""
-        if P.refine is not None:
-            return self._enqueue_refine(P, guidance, want_float=want_float, taps=taps)
+        """Enqueue the whole sampler on the current stream (this is what gets captured): a chain of passes, each the LCM steps
+        over one schedule.  A plain plan is the one pass over timesteps(steps).  A refinement plan P.refine = (d, run, cached) is
+        that pass (unless the chain starts from cached latents in P.xk[0], re-noised by lcm_latents_renoise) followed by `run`
+        passes over the strength-cut schedule.  A pass that another one follows ends in the hand-over step (x^k to P.xk, the
+        re-noised state of the next pass to P.lat, one launch); the last pass ends in the plain `last` step and only its x goes
+        through the VAE."""
         B, UB, h, w = P.B, P.UB, P.h, P.w
         unet, vae = P.lane.unet, P.lane.vae
-        ts = self.sched.timesteps(P.steps)
-        if P.do_cfg:
+        pred = self.sched.prediction_type
+        d, run, cached = P.refine if P.refine is not None else (1.0, 0, False)
+        passes = [] if cached else [self.sched.timesteps(P.steps)]
+        nsa = nsb = None
+        if run:
+            ts_cut = self.sched.timesteps(P.steps, d)
+            nsa, nsb = self.sched.renoise_coefficients(ts_cut[0])
+            passes += [ts_cut] * run
+        ni = 0                                        # next tensor of P.noise, in draw order
+        if cached:
+            ops.latents_renoise(P.xk[0], P.noise[0], nsa, nsb, P.lat, B, h, w, dup=P.do_cfg)
+            ni = 1
+        elif P.do_cfg:
             P.lat[:B].copy_(P.lat0)
             P.lat[B:].copy_(P.lat0)
         else:
@@ -241,9 +247,17 @@ class LcmHipPipeline:
         kv = unet.encode_context(P.ehs, UB)
         aug = unet.encode_added(P.add_in, UB) if unet.has_added else None
         wemb = P.wemb if unet.has_cond else None
-        # the time-embedding MLP + all time_emb_proj of EVERY step ahead of the loop (they depend on the schedule and the
-        # request's guidance only): 5 launches per pass instead of 4 per step
-        ta_all = unet.time_embed_all([int(t) for t in ts], wemb, UB, aug) if len(ts) <= unet.MAX_HOISTED_STEPS else None
+        # under classifier-free guidance rows [0,B) = negative prompt, [B,2B) = prompt: the step updates the prompt half
+        state = P.lat[B:] if P.do_cfg else P.lat
+        eps = P.eps[B:] if P.do_cfg else P.eps
+        kw = dict(eps_uncond=P.eps[:B], guidance=guidance) if P.do_cfg else {}
+
+        def hoist(net, ts, wemb, aug):
+            # the time-embedding MLP + all time_emb_proj of EVERY step of a pass ahead of its steps (they depend on the schedule
+            # and the request's guidance only): 5 launches per pass instead of 4 per step; None: per step, inside forward
+            return net.time_embed_all([int(t) for t in ts], wemb, UB, aug) if len(ts) <= net.MAX_HOISTED_STEPS else None
+
+        ta_all, ta_c, ta_ts = hoist(unet, passes[0], wemb, aug), None, passes[0]
         cn = None
         if P.control is not None:
             # ControlNet: the hint embedding ONCE per request (it depends on the hint alone), repeated for the unconditional
@@ -256,79 +270,34 @@ class LcmHipPipeline:
             if taps is not None:
                 taps["cn.hint_emb"] = P.hint_emb[:n1].reshape(B, h, w, -1).permute(0, 3, 1, 2).float().cpu()
             kv_c = cn.encode_context(P.ehs, UB)
-            ta_c = cn.time_embed_all([int(t) for t in ts], None, UB) if len(ts) <= cn.MAX_HOISTED_STEPS else None
-        for i, t in enumerate(ts):
-            control = None
-            if cn is not None:
-                feats, mid_f = cn.forward(P.lat, int(t), kv_c, UB, h, w, P.hint_emb, taps=taps if i == 0 else None,
-                                          ta=ta_c[i * UB:(i + 1) * UB] if ta_c is not None else None)
-                control = (cn, feats, mid_f, P.control)
-            unet.forward(P.lat, int(t), kv, wemb, UB, h, w, P.eps, taps=taps if i == 0 else None, aug=aug,
-                         ta=ta_all[i * UB:(i + 1) * UB] if ta_all is not None else None, control=control)
-            coef, last = self.sched.step_coefficients(ts, i)
-            noise = P.noise[min(i, P.noise.shape[0] - 1)]
-            pred = self.sched.prediction_type
-            if P.do_cfg:   # rows [0,B) = negative prompt, [B,2B) = prompt
-                ops.scheduler_step(P.eps[B:], P.lat[B:], noise, coef, last, B, h, w, eps_uncond=P.eps[:B], guidance=guidance,
-                                   pred=pred)
-                P.lat[:B].copy_(P.lat[B:])
-            else:
-                ops.scheduler_step(P.eps, P.lat, noise, coef, last, B, h, w, pred=pred)
-        final = P.lat[B:] if P.do_cfg else P.lat
-        ops.latents_pool8(final, P.pool8, B, h, w)
-        if want_float and P.img_f32 is None:
-            P.img_f32 = torch.zeros(B, h * 8, w * 8, 3, dtype=torch.float32, device=self.device)
-        vae.decode(final, B, h, w, P.rgb, img_f32=P.img_f32 if want_float else None, taps=taps)
-        return final
-
-    def _enqueue_refine(self, P: _Plan, guidance: float, want_float=False, taps=None):
-        """The refinement chain of P.refine = (d, run, cached) as one enqueue (one captured graph): the plain pass that gives x^0
-        (unless the chain starts from cached latents in P.xk[0], re-noised by lcm_latents_renoise), then `run` passes over the
-        strength-cut schedule.  A pass that another one follows ends in the hand-over step (x^k to P.xk, the re-noised state of
-        the next pass to P.lat, one launch); the last pass ends in the plain `last` step and only its x goes through the VAE."""
-        B, UB, h, w = P.B, P.UB, P.h, P.w
-        unet, vae = P.lane.unet, P.lane.vae
-        d, run, cached = P.refine
-        pred = self.sched.prediction_type
-        ts_cut = self.sched.timesteps(P.steps, d)
-        nsa, nsb = self.sched.renoise_coefficients(ts_cut[0])
-        ni = 0                                        # next tensor of P.noise, in draw order
-        if cached:
-            ops.latents_renoise(P.xk[0], P.noise[0], nsa, nsb, P.lat, B, h, w, dup=P.do_cfg)
-            ni = 1
-            passes = [ts_cut] * run
-        else:
-            if P.do_cfg:
-                P.lat[:B].copy_(P.lat0)
-                P.lat[B:].copy_(P.lat0)
-            else:
-                P.lat.copy_(P.lat0)
-            passes = [self.sched.timesteps(P.steps)] + [ts_cut] * run
-        kv = unet.encode_context(P.ehs, UB)
-        aug = unet.encode_added(P.add_in, UB) if unet.has_added else None
-        wemb = P.wemb if unet.has_cond else None
-        state = P.lat[B:] if P.do_cfg else P.lat
-        eps = P.eps[B:] if P.do_cfg else P.eps
-        kw = dict(eps_uncond=P.eps[:B], guidance=guidance) if P.do_cfg else {}
-        ta_all, ta_ts = None, None
+            ta_c = hoist(cn, passes[0], None, None)
         for j, ts in enumerate(passes):
-            if len(ts) <= unet.MAX_HOISTED_STEPS and (ta_ts is None or list(ta_ts) != list(ts)):
-                ta_all, ta_ts = unet.time_embed_all([int(t) for t in ts], wemb, UB, aug), ts    # once per distinct schedule
+            if list(ts) != list(ta_ts):               # once per distinct schedule, reused across consecutive equal passes
+                ta_all, ta_ts = hoist(unet, ts, wemb, aug), ts
+                if cn is not None:
+                    ta_c = hoist(cn, ts, None, None)
             for i, t in enumerate(ts):
-                unet.forward(P.lat, int(t), kv, wemb, UB, h, w, P.eps, taps=taps if (i == 0 and j == 0) else None, aug=aug,
-                             ta=ta_all[i * UB:(i + 1) * UB] if ta_all is not None else None)
+                rows, tap1 = slice(i * UB, (i + 1) * UB), taps if (i == 0 and j == 0) else None
+                control = None
+                if cn is not None:
+                    feats, mid_f = cn.forward(P.lat, int(t), kv_c, UB, h, w, P.hint_emb, taps=tap1,
+                                              ta=ta_c[rows] if ta_c is not None else None)
+                    control = (cn, feats, mid_f, P.control)
+                unet.forward(P.lat, int(t), kv, wemb, UB, h, w, P.eps, taps=tap1, aug=aug,
+                             ta=ta_all[rows] if ta_all is not None else None, control=control)
                 coef, last = self.sched.step_coefficients(ts, i)
                 if last and j < len(passes) - 1:
                     ops.scheduler_step_handover(eps, state, P.noise[ni], P.xk[j + 1 if cached else j], coef, nsa, nsb, B, h, w,
                                                 pred=pred, dup=P.do_cfg, **kw)
                     ni += 1
-                else:
+                else:                                 # the final `last` step reads no noise: any tensor of P.noise serves
                     ops.scheduler_step(eps, state, P.noise[min(ni, P.noise.shape[0] - 1)], coef, last, B, h, w, pred=pred, **kw)
                     if not last:
                         ni += 1
                         if P.do_cfg:
-                            P.lat[:B].copy_(P.lat[B:])
-        P.xk[run].copy_(state)
+                            P.lat[:B].copy_(state)
+        if P.xk is not None:
+            P.xk[run].copy_(state)
         ops.latents_pool8(state, P.pool8, B, h, w)
         if want_float and P.img_f32 is None:
             P.img_f32 = torch.zeros(B, h * 8, w * 8, 3, dtype=torch.float32, device=self.device)
@@ -396,10 +365,8 @@ class LcmHipPipeline:
             try:
                 torch.cuda.synchronize(self.device)
                 ops.set_stream_workspace(L.stream, L.splitk_ws, forget=True)      # only if the entry is still this lane's
-                ops.set_stream_workspace(L.side, L.side_ws, forget=True)
                 ops.release_stream(L.stream)
-                ops.release_stream(L.side)
-                L.stream = L.side = None
+                L.stream = None
             except Exception:
                 pass
 

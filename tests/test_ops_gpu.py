@@ -676,7 +676,7 @@ def test_attention_peaked_softmax():
 
 @pytest.mark.parametrize("heads,Sq,Sk,d", [(8, 1024, 1024, 40), (8, 256, 77, 80), (4, 64, 64, 160), (10, 300, 300, 64)])
 def test_attention_prescaled_q(heads, Sq, Sk, d):
-    """scale <= 0: q arrives with d^-0.5 * log2(e) already in it (model.Q_PRESCALE folds it into the to_q weights) -- the
+    """scale <= 0: q arrives with d^-0.5 * log2(e) already in it (model._pack_transformer folds it into the to_q weights) -- the
     streaming, the register-staged and the d = 160 kernels against torch SDPA in fp32 on the unscaled q."""
     B, C = 2, heads * d
     q, k, v = rnd(B * Sq, C, seed=1), rnd(B * Sk, C, seed=2), rnd(B * Sk, C, seed=3)
