@@ -345,6 +345,24 @@ int lcm_scheduler_step_handover(const void* eps, const void* eps_uncond, float g
                                 const float* coef6, float next_sqrt_a, float next_sqrt_b, int prediction_type, int B, int h, int w,
                                 int dup, void* stream);
 
+/* ---- hires fix: the hand-over between two sizes ----
+ * lat_out = fmaf(sqrt_b, noise, sqrt_a * up(x0)) in one launch: x0 fp32 NCHW [B,4,h,w] (the denoised latents of the
+ * low-resolution pass) is upscaled to [B,4,H,W] with one of A1111's latent upscalers and re-noised like lcm_latents_renoise.
+ * All modes are torch.nn.functional.interpolate(..., align_corners=False, antialias=False):
+ *   LCM_UPSCALE_BILINEAR       "Latent"                  bilinear, source coordinate clamped at 0
+ *   LCM_UPSCALE_BICUBIC        "Latent (bicubic)"        bicubic, A = -0.75, indices clamped, coordinate not clamped
+ *   LCM_UPSCALE_NEAREST_EXACT  "Latent (nearest-exact)"  source index floor((dst + 0.5) in / out)
+ * A source coordinate is the exact rational ((2 dst + 1) in - out) / (2 out): integer floor, and a fraction that is one
+ * correctly rounded fp32 division -- the weights depend on (dst, in, out) only (Determinism, above).  Taps of weight 0 are
+ * left out, so H == h, W == w gives lcm_latents_renoise's bits.  x_up != NULL also receives up(x0) (fp32 [B,4,H,W]).
+ * dup != 0: lat_out is [2B,4,H,W] and both halves get the value.  Any 1 <= h <= H <= 4h, 1 <= w <= W <= 4w with H, W <= 16384
+ * and B*4*H*W < 2^30; no alignment requirement.  Anything else is LCM_EINVAL before anything is enqueued. */
+#define LCM_UPSCALE_BILINEAR 0
+#define LCM_UPSCALE_BICUBIC 1
+#define LCM_UPSCALE_NEAREST_EXACT 2
+int lcm_latents_upscale_renoise(const void* x0, int h, int w, const void* noise, float sqrt_a, float sqrt_b, int mode, void* x_up,
+                                void* lat_out, int B, int H, int W, int dup, void* stream);
+
 /* ---- adaptive_avg_pool2d(lat,(8,8)) -> fp16 [B,4,8,8] (run_job_with_latents, backends/cuda_worker.py:299-304) */
 int lcm_latents_pool8(const void* lat, void* out_f16, int B, int h, int w, void* stream);
 

@@ -36,6 +36,7 @@ from ..prompt import HipPromptEncoder
 from ..scheduler import LCMSchedule
 from .. import weights as _weights
 from . import controlnet as _controlnet
+from . import hires as _hires
 from . import refine as _refine
 
 
@@ -248,7 +249,8 @@ class _Engine:
         # device so that pass p of a request starts from its pass p - 1.  Plain requests never touch it.
         self.refine_cache = _refine.RefineCache(_refine.cache_bytes_from_env())
         self._stats_lock = threading.Lock()
-        self.stats = dict(unet_evals=0, refine_cache_hits=0, refine_cache_misses=0, refine_cache_puts=0, controlnet_evals=0)
+        self.stats = dict(unet_evals=0, refine_cache_hits=0, refine_cache_misses=0, refine_cache_puts=0, controlnet_evals=0,
+                          hires_requests=0)
         # ControlNet: where it comes from (CONTROLNET=<dir or file> | "synthetic" | None); loaded on the first request that
         # carries a hint, released with the pipeline
         self.controlnet_src = None
@@ -354,6 +356,8 @@ class _Engine:
                     with self._stats_lock:
                         self.stats["unet_evals"] += steps
                         self.stats["controlnet_evals"] += steps
+                elif _hires.is_hires_key(key):
+                    res = self._run_hires(pipe, key, items, noises, pe, kw, lane, stream)
                 elif len(key) > 6:
                     res = self._run_refine(pipe, key, items, noises, pe, kw, lane, stream)
                 else:
@@ -412,6 +416,41 @@ class _Engine:
                 self.stats["refine_cache_puts"] += puts
             for b, i in enumerate(idx):
                 res[i] = (out["rgb"][b], out["pool8"][b:b + 1])
+        return res
+
+    def _run_hires(self, pipe, key, items, noises, pe, kw, lane, stream):
+        """The passes of a hires batch (key = plain key + (KEY_TAG, target width, target height, hr_steps, strength, mode)).  The
+        second stage at a large target can need more split-K workspace than the lane has: the need is computed from the plan
+        and the batch runs as passes of the largest plan size that fits (bit-neutral: a request's bytes do not depend on its
+        batch) -- a request never fails on workspace a smaller pass would have served."""
+        width, height, steps, g = key[:4]
+        tw, th, hr_steps, strength, mode = key[7:12]
+        cap = pipe.hires_batch_cap(tw, th, hr_steps, strength, g, lane=lane, sizes=self.batch_sizes)
+        n = len(items)
+        res = [None] * n
+
+        def rows(x, idx):                            # per-request conditioning rows of a sub-batch
+            if isinstance(x, torch.Tensor) and x.dim() > 0 and x.shape[0] == n:
+                return x[idx]
+            return x
+        evals = 0
+        for i0 in range(0, n, min(cap, n)):
+            idx = list(range(i0, min(n, i0 + cap)))
+            if len(idx) not in self.batch_sizes:     # a tail that is no plan size: its last item repeated (results dropped)
+                idx += [idx[-1]] * (min(s for s in self.batch_sizes if s >= len(idx)) - len(idx))
+            whole = idx == list(range(n))
+            with torch.cuda.stream(stream):          # the rows are gathered on the lane's stream, behind the text encoder
+                sub_pe = pe if whole else pe[idx]
+                sub_kw = kw if whole else {name: rows(v, idx) for name, v in kw.items()}
+            out = pipe.generate(sub_pe, [items[i][1] for i in idx], width, height, steps, g,
+                                noises=[noises[i] for i in idx] if noises is not None else None, lane=lane,
+                                hires=(tw, th, hr_steps, strength, mode), **sub_kw)
+            evals += out["unet_evals"]
+            for b, i in enumerate(idx):
+                res[i] = (out["rgb"][b], out["pool8"][b:b + 1])
+        with self._stats_lock:
+            self.stats["unet_evals"] += evals
+            self.stats["hires_requests"] += len({id(it) for it in items})
         return res
 
     def start_batcher(self):
@@ -663,7 +702,9 @@ class HipLcmWorker:
     def _job_key(req):
         """What must agree for jobs to share one batched pass: geometry, step count, guidance and style merge -- and, for a
         refinement request (``denoise_strength`` / ``pass_number``, backends/refine.py), its strength and pass number: those
-        get a key of their own (the plain fields plus (d, p)) and never share a pass with plain requests."""
+        get a key of their own (the plain fields plus (d, p)) and never share a pass with plain requests.  Hires requests
+        (``enable_hr``, backends/hires.py) coalesce among themselves: the plain key + ("hires", target size, hr_steps, strength,
+        mode)."""
         width, height = parse_size(req.size)
         sl = getattr(req, "style_lora", None)
         style_id = getattr(sl, "style", None) if sl else None
@@ -673,6 +714,13 @@ class HipLcmWorker:
         key = (width, height, int(req.num_inference_steps), float(req.guidance_scale), style_id, level)
         rf = _refine.parse_refine(req)
         ctl = _controlnet.parse_control(req)
+        hr = _hires.parse_hires(req, width, height, key[2])
+        if hr is not None:
+            if rf is not None:
+                raise RuntimeError("enable_hr is not combined with refinement (denoise_strength < 1 or pass_number > 1)")
+            if ctl is not None:
+                raise RuntimeError("enable_hr is not combined with controlnet_image")
+            return key + (_hires.KEY_TAG,) + hr
         if ctl is not None:
             # ControlNet jobs coalesce among themselves: the plain key + the conditioning scale (the hint is per image)
             if rf is not None:
@@ -699,6 +747,14 @@ class HipLcmWorker:
             if key[0] % 8 == 0 and key[1] % 8 == 0 and key[0] > 0 and key[1] > 0 and key[2] >= 1:
                 noise = draw_noise(seed, key[1] // 8, key[0] // 8, n_draws - 1, eng.pipe.sched.init_noise_sigma)
             return (req, seed, noise, hint)
+        if _hires.is_hires_key(key):                 # the schedule's own error first, then the draws at both shapes
+            tw, th, hr_steps, strength = key[7:11]
+            _hires.check_schedule(eng.pipe.sched, hr_steps, strength)
+            if all(v % 8 == 0 and v > 0 for v in (key[0], key[1], tw, th)) and key[2] >= 1:
+                from ..pipeline import draw_noise_hires
+                noise = draw_noise_hires(seed, key[1] // 8, key[0] // 8, key[2], th // 8, tw // 8, hr_steps,
+                                         eng.pipe.sched.init_noise_sigma)
+            return (req, seed, noise)
         if len(key) > 6:                             # refinement: the schedule's own error first, then the whole chain's draws
             try:
                 eng.pipe.sched.timesteps(key[2], key[6])
@@ -936,6 +992,12 @@ class HipLcmSDXLWorker(HipLcmWorker):
     classifier-free guidance when guidance_scale > 1 (negative conditioning = zeros, force_zeros_for_empty_prompt)."""
 
     FAMILY = "sdxl"
+
+    @staticmethod
+    def _job_key(req):
+        if getattr(req, "enable_hr", None):
+            raise RuntimeError("enable_hr: hires fix is not served by the SDXL worker (SD1.5 and SD 2.x only)")
+        return HipLcmWorker._job_key(req)
 
     def _synthetic_weights(self):
         from ..config import SDXL_UNET, unet_config, vae_config

@@ -58,6 +58,7 @@ _SIGS = {
     "lcm_scheduler_step_ex": [_vp, _vp, _f, _vp, _vp, C.POINTER(C.c_float), _i, _i, _i, _i, _i, _vp],
     "lcm_latents_pool8": [_vp, _vp, _i, _i, _i, _vp],
     "lcm_latents_renoise": [_vp, _vp, _f, _f, _vp, _i, _i, _i, _i, _vp],
+    "lcm_latents_upscale_renoise": [_vp, _i, _i, _vp, _f, _f, _i, _vp, _vp, _i, _i, _i, _i, _vp],
     "lcm_scheduler_step_handover": [_vp, _vp, _f, _vp, _vp, _vp, C.POINTER(C.c_float), _f, _f, _i, _i, _i, _i, _i, _vp],
     "lcm_png_encode_rgb8": [_vp, _i, _i, C.c_longlong, _i, _vp, C.c_longlong, C.POINTER(C.c_longlong)],
     "lcm_stream_create": [C.POINTER(_vp)],
@@ -200,3 +201,8 @@ def check(rc: int, what: str = ""):
 # prediction types of lcm_scheduler_step_ex (include/lcm_hip.h)
 LCM_PRED_EPSILON, LCM_PRED_V, LCM_PRED_SAMPLE = 0, 1, 2
 PREDICTION_TYPES = {"epsilon": LCM_PRED_EPSILON, "v_prediction": LCM_PRED_V, "sample": LCM_PRED_SAMPLE}
+
+# latent upscalers of lcm_latents_upscale_renoise (include/lcm_hip.h), by A1111's ``hr_upscaler`` name
+LCM_UPSCALE_BILINEAR, LCM_UPSCALE_BICUBIC, LCM_UPSCALE_NEAREST_EXACT = 0, 1, 2
+UPSCALE_MODES = {"Latent": LCM_UPSCALE_BILINEAR, "Latent (bicubic)": LCM_UPSCALE_BICUBIC,
+                 "Latent (nearest-exact)": LCM_UPSCALE_NEAREST_EXACT}

@@ -470,6 +470,17 @@ def latents_renoise(x0, noise, sqrt_a, sqrt_b, lat, B, h, w, *, dup=False):
     return lat
 
 
+def latents_upscale_renoise(x0, h, w, noise, sqrt_a, sqrt_b, mode, lat, B, H, W, *, x_up=None, dup=False):
+    """lat <- sqrt_a up(x0) + sqrt_b noise: x0 fp32 [B,4,h,w] upscaled to [B,4,H,W] by latent upscaler ``mode`` (0 bilinear,
+    1 bicubic, 2 nearest-exact: lib.UPSCALE_MODES) and re-noised, one launch.  x_up: optional fp32 [B,4,H,W] that receives
+    up(x0); dup: ``lat`` is [2B,4,H,W] and both halves are written."""
+    L = _lib.load()
+    _lib.check(L.lcm_latents_upscale_renoise(_p(x0), int(h), int(w), _p(noise), float(sqrt_a), float(sqrt_b), int(mode), _p(x_up),
+                                             _p(lat), int(B), int(H), int(W), int(bool(dup)), _stream()),
+               "lcm_latents_upscale_renoise")
+    return lat
+
+
 def scheduler_step_handover(eps, lat, noise, xk, coef6, next_sqrt_a, next_sqrt_b, B, h, w, *, eps_uncond=None, guidance=1.0,
                             pred="epsilon", dup=False):
     """The last step of a refinement pass that another pass follows: xk <- the denoised latents (the bits of the ``last`` step),

@@ -8,6 +8,11 @@ latents from the request's generator -> [UNet -> LCMScheduler.step] x n -> /scal
 RNG contract: each request owns a CPU ``torch.Generator`` seeded with its seed; draws are
 latents[1,4,h,w] then one noise tensor per non-final step.  All draws happen on the host BEFORE the graph is
 launched, so the captured graph is RNG-free and replays for any seed.
+
+A hires request (``generate(..., hires=)``) keeps that one generator: it draws the plain request's tensors first --
+latents[1,4,h,w], then steps - 1 step noises -- and then, at the target shape, the re-noise tensor [1,4,H2/8,W2/8] and
+hr_steps - 1 step noises (``draw_noise_hires``).  Its bytes therefore depend only on (prompt, seed, size, steps, guidance, style,
+target size, hr_steps, strength, mode) -- not on the batch, the lane or what ran before.
 """
 from __future__ import annotations
 
@@ -59,6 +64,16 @@ def draw_noise(seed: int, h: int, w: int, n_extra: int, sigma: float = 1.0):
     return lat, extra
 
 
+def draw_noise_hires(seed: int, h: int, w: int, steps: int, h2: int, w2: int, hr_steps: int, sigma: float = 1.0):
+    """A hires request's RNG stream (module docstring) -> (latents, the steps - 1 step noises at [1,4,h,w], the re-noise tensor
+    followed by the hr_steps - 1 step noises at [1,4,h2,w2])."""
+    g = torch.Generator(device="cpu").manual_seed(int(seed))
+    lat = torch.randn((1, 4, h, w), generator=g, dtype=torch.float32) * sigma
+    lo = [torch.randn((1, 4, h, w), generator=g, dtype=torch.float32) for _ in range(int(steps) - 1)]
+    hi = [torch.randn((1, 4, h2, w2), generator=g, dtype=torch.float32) for _ in range(int(hr_steps))]
+    return lat, lo, hi
+
+
 _DEFAULT_WS = {}
 
 
@@ -101,14 +116,18 @@ class _Lane:
 
 class _Plan:
     """Buffers + captured graph for one (B, h, w, steps, cfg) key.  refine = (strength, passes to run, starts from cached
-    latents) makes it the plan of a refinement chain; None: the plain sampler (LcmHipPipeline._enqueue runs both)."""
+    latents) makes it the plan of a refinement chain; None: the plain sampler (LcmHipPipeline._enqueue runs both).  The two stages of a hires request
+    are plan kinds of their own: kind "latents" is the plain sampler without the VAE decode and the RGB epilogue (its result is
+    P.lat), kind "from-state" a started-from-latents refinement plan whose first state the hand-over launch has already written
+    to P.lat."""
 
-    def __init__(self, pipe, B, h, w, steps, do_cfg, lane=None, refine=None, control=None):
+    def __init__(self, pipe, B, h, w, steps, do_cfg, lane=None, refine=None, control=None, kind=None):
         # Every zero-fill below must be ordered before the first use on the lane's (non-blocking) stream: allocate
         # under that stream, or a fill still queued on the null stream can land AFTER the request's uploads.
         self.lane = lane if lane is not None else pipe.lanes[0]
         self.refine = refine
         self.control = control        # conditioning scale of a ControlNet plan (baked into the captured GEMMs); None: no hint
+        self.kind = kind              # None | "latents" | "from-state" (the stages of a hires request)
         with torch.cuda.stream(self.lane.stream):
             self._init(pipe, B, h, w, steps, do_cfg)
 
@@ -237,7 +256,8 @@ class LcmHipPipeline:
             passes += [ts_cut] * run
         ni = 0                                        # next tensor of P.noise, in draw order
         if cached:
-            ops.latents_renoise(P.xk[0], P.noise[0], nsa, nsb, P.lat, B, h, w, dup=P.do_cfg)
+            if P.kind != "from-state":                # hires stage 2: lcm_latents_upscale_renoise wrote P.lat (and P.xk[0])
+                ops.latents_renoise(P.xk[0], P.noise[0], nsa, nsb, P.lat, B, h, w, dup=P.do_cfg)
             ni = 1
         elif P.do_cfg:
             P.lat[:B].copy_(P.lat0)
@@ -298,19 +318,23 @@ class LcmHipPipeline:
                             P.lat[:B].copy_(state)
         if P.xk is not None:
             P.xk[run].copy_(state)
+        if P.kind == "latents":                       # hires stage 1: nobody sees this picture, so nothing decodes it
+            return state
         ops.latents_pool8(state, P.pool8, B, h, w)
         if want_float and P.img_f32 is None:
             P.img_f32 = torch.zeros(B, h * 8, w * 8, 3, dtype=torch.float32, device=self.device)
         vae.decode(state, B, h, w, P.rgb, img_f32=P.img_f32 if want_float else None, taps=taps)
         return state
 
-    def plan(self, B, h, w, steps, do_cfg=False, guidance=None, lane=0, refine=None, control=None) -> _Plan:
+    def plan(self, B, h, w, steps, do_cfg=False, guidance=None, lane=0, refine=None, control=None, kind=None) -> _Plan:
         # classifier-free guidance bakes the guidance value into the captured step kernels: one plan per value
         key = (B, h, w, steps, do_cfg, round(float(guidance), 4) if do_cfg and guidance is not None else None)
         if refine is not None:                       # (d, passes to run, starts from cached latents): a chain of its own
             key = key + (round(float(refine[0]), 6), int(refine[1]), bool(refine[2]))
         if control is not None:                      # a ControlNet plan: "control" + the conditioning scale its GEMMs bake in
             key = key + ("control", round(float(control), 6))
+        if kind is not None:                         # a stage of a hires request: "latents" (no decode) / "from-state"
+            key = key + (kind,)
         L = self.lane(lane)
         P = L.plans.get(key)
         if P is None:
@@ -318,7 +342,7 @@ class LcmHipPipeline:
                 P = L.plans.get(key)
                 if P is None:
                     P = _Plan(self, B, h, w, steps, do_cfg, L, refine=refine,
-                              control=None if control is None else round(float(control), 6))
+                              control=None if control is None else round(float(control), 6), kind=kind)
                     L.plans[key] = P
         return P
 
@@ -377,10 +401,158 @@ class LcmHipPipeline:
             pass
 
     # ------------------------------------------------------------------------------------------
+    def _upload_text(self, P: _Plan, pe, negative_embeds, guidance_scale):
+        """Prompt embeddings (negative ones in front under classifier-free guidance) and the guidance embedding into the plan's
+        buffers, on the current stream."""
+        B = P.B
+        pe16 = pe.to(torch.float16).reshape(B * TEXT_SEQ_LEN, -1)
+        if P.do_cfg:
+            ne16 = torch.as_tensor(negative_embeds).to(torch.float16).reshape(B * TEXT_SEQ_LEN, -1)
+            P.ehs[:B * TEXT_SEQ_LEN].copy_(ne16, non_blocking=True)
+            P.ehs[B * TEXT_SEQ_LEN:].copy_(pe16, non_blocking=True)
+        else:
+            P.ehs.copy_(pe16, non_blocking=True)
+        if self.unet.has_cond:
+            gs = np.full((B,), float(guidance_scale) - 1.0, dtype=np.float32)
+            P.wemb.copy_(torch.from_numpy(guidance_scale_embedding(gs, P.wemb.shape[1])).to(torch.float16),
+                         non_blocking=True)
+
+    def _ensure_graph(self, P: _Plan, guidance_scale):
+        """Tune, warm up (allocates every scratch buffer) and capture the plan's graph on its lane's stream, once."""
+        if P.graph is None:
+            with self._build_lock:
+                if P.graph is None:
+                    self.tune(P)
+                    self._enqueue(P, guidance_scale)
+                    P.lane.stream.synchronize()
+                    g = ops.Graph()
+                    with g:
+                        self._enqueue(P, guidance_scale)
+                    P.graph = g
+
+    def splitk_need(self, P: _Plan) -> int:
+        """An upper bound of the split-K workspace bytes a pass of P's size needs PER IMAGE ROW of the UNet batch, from the plan's
+        own launches: the K partition of a layer is a property of its per-image shape (include/lcm_hip.h, Determinism), so a
+        batch of n needs at most n times this (a batched launch that fills the chip keeps the parts in registers and needs
+        less).  P must be a batch-1 plan: one eager pass of it is recorded -- a pass that does not fit at batch 1 raises the
+        library's error."""
+        if P.B != 1:
+            raise LcmHipError("splitk_need: a batch-1 plan, please")
+        need = getattr(P, "_splitk_need", None)
+        if need is None:
+            from . import autotune
+            with self._build_lock, torch.cuda.stream(P.lane.stream):
+                with ops.recording() as recs:
+                    self._enqueue(P, 1.0)
+                P.lane.stream.synchronize()
+            need = 0
+            for key, meta, _ in recs:
+                if key is None or not meta.get("splittable"):
+                    continue
+                m_img = meta.get("m_img", key[1])
+                sp = autotune._canonical_splits(key, meta, m_img)
+                if sp > 1:
+                    need = max(need, 4 * sp * m_img * key[2])
+            P._splitk_need = need
+        return need
+
+    def hires_batch_cap(self, width, height, hr_steps, strength, guidance_scale=1.0, lane=0, sizes=(1, 2, 4, 8)) -> int:
+        """The largest pass size of ``sizes`` whose second stage at width x height fits the lane's split-K workspace (at least
+        the smallest: a batch-1 pass that does not fit raises the library's loud error when it runs)."""
+        do_cfg = (guidance_scale > 1.0) and not self.unet.has_cond
+        P = self.plan(1, height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR, int(hr_steps), do_cfg, guidance_scale, lane=lane,
+                      refine=(float(strength), 1, True), kind="from-state")
+        per_request = self.splitk_need(P) * (2 if do_cfg else 1)      # classifier-free guidance: two UNet rows per request
+        have = P.lane.splitk_ws.numel() * 4
+        fit = [n for n in sorted(sizes) if n * per_request <= have]
+        return fit[-1] if fit else min(sizes)
+
     @torch.inference_mode()
-    def generate(self, prompt_embeds, seeds, width, height, steps, guidance_scale=1.0, negative_embeds=None,
+    def generate_hires(self, prompt_embeds, seeds, width, height, steps, hires, guidance_scale=1.0, negative_embeds=None,
+                       want_float=False, noises=None, lane=0):
+        """Hires fix: sample at (width, height) for ``steps`` steps, upscale the denoised latents to (W2, H2) with latent upscaler
+        ``mode`` (lib.UPSCALE_MODES), re-noise them to the first timestep of ``timesteps(hr_steps, strength)``, run ``hr_steps``
+        steps there and decode once.  hires = (W2, H2, hr_steps, strength, mode).  Three launches on the lane's stream with
+        nothing copied to the host in between: the "latents" plan at the base size (no VAE decode), lcm_latents_upscale_renoise
+        into the state of the "from-state" refinement plan at the target size, that plan.  noises: optional per-request
+        ``draw_noise_hires`` results.  Returns the usual dict at the target size plus ``lowres_latents`` (host fp32 [B,4,h,w],
+        the plain request's final latents bit for bit) and ``unet_evals`` = steps + hr_steps (doubled under classifier-free
+        guidance); with want_float (eager launches) also ``image`` and ``upscaled_latents`` (host fp32 [B,4,H2/8,W2/8])."""
+        torch.cuda.set_device(self.device)
+        pe = torch.as_tensor(prompt_embeds)
+        B = pe.shape[0]
+        W2, H2, hr_steps, strength, mode = hires
+        W2, H2, steps, hr_steps, strength, mode = int(W2), int(H2), int(steps), int(hr_steps), float(strength), int(mode)
+        check_size(width, height)
+        check_size(W2, H2)
+        if self.unet.has_added:
+            raise LcmHipError("hires fix is not served for SDXL-family UNets")
+        if mode not in (0, 1, 2):
+            raise LcmHipError(f"unknown latent upscaler mode {mode}: expected 0 (bilinear), 1 (bicubic) or 2 (nearest-exact)")
+        if not (width <= W2 <= 4 * width and height <= H2 <= 4 * height):
+            raise LcmHipError(f"hires target {W2}x{H2} outside [1, 4] x the base size {width}x{height}")
+        do_cfg = (guidance_scale > 1.0) and not self.unet.has_cond
+        if do_cfg and negative_embeds is None:
+            raise LcmHipError("classifier-free guidance needs negative_embeds")
+        self.sched.timesteps(steps)
+        ts2 = self.sched.timesteps(hr_steps, strength)   # diffusers' error for hr_steps > original_steps x strength, before any plan
+        nsa, nsb = self.sched.renoise_coefficients(ts2[0])
+        h, w, h2, w2 = height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR, H2 // VAE_SCALE_FACTOR, W2 // VAE_SCALE_FACTOR
+        P1 = self.plan(B, h, w, steps, do_cfg, guidance_scale, lane=lane, kind="latents")
+        P2 = self.plan(B, h2, w2, hr_steps, do_cfg, guidance_scale, lane=lane, refine=(strength, 1, True), kind="from-state")
+        stream = P1.lane.stream
+        with torch.cuda.stream(stream):
+            for b, s in enumerate(seeds):
+                l0, lo, hi = noises[b] if noises is not None else draw_noise_hires(s, h, w, steps, h2, w2, hr_steps,
+                                                                                   self.sched.init_noise_sigma)
+                if len(lo) != steps - 1 or len(hi) != hr_steps:
+                    raise LcmHipError(f"request {b}: {len(lo)} + {len(hi)} noise tensors drawn ahead, the chain needs "
+                                      f"{steps - 1} + {hr_steps}")
+                P1.h_lat[b].copy_(l0[0])
+                for i, n in enumerate(lo):
+                    P1.h_noise[i, b].copy_(n[0])
+                for i, n in enumerate(hi):
+                    P2.h_noise[i, b].copy_(n[0])
+            eager = (not self.use_graph) or want_float
+            if not eager:                            # both graphs first: a warm-up pass overwrites its plan's state
+                self._ensure_graph(P1, guidance_scale)
+                self._ensure_graph(P2, guidance_scale)
+            P1.lat0.copy_(P1.h_lat, non_blocking=True)
+            P1.noise.copy_(P1.h_noise, non_blocking=True)
+            P2.noise.copy_(P2.h_noise, non_blocking=True)
+            self._upload_text(P1, pe, negative_embeds, guidance_scale)
+            self._upload_text(P2, pe, negative_embeds, guidance_scale)
+            # ---- stage 1 -> hand-over -> stage 2, in stream order ----
+            if eager:
+                with self._build_lock:
+                    self._enqueue(P1, guidance_scale)
+            else:
+                P1.graph.launch()
+            low = P1.lat[B:] if do_cfg else P1.lat
+            ops.latents_upscale_renoise(low, h, w, P2.noise[0], nsa, nsb, mode, P2.lat, B, h2, w2, x_up=P2.xk[0], dup=do_cfg)
+            if eager:
+                with self._build_lock:
+                    self._enqueue(P2, guidance_scale, want_float=want_float)
+            else:
+                P2.graph.launch()
+            final = P2.lat[B:] if do_cfg else P2.lat
+            P2.h_rgb.copy_(P2.rgb, non_blocking=True)
+            P2.h_pool8.copy_(P2.pool8, non_blocking=True)
+            P2.h_latout.copy_(final, non_blocking=True)
+            P1.h_latout.copy_(low, non_blocking=True)
+            stream.synchronize()
+        out = dict(rgb=P2.h_rgb.numpy().copy(), latents=P2.h_latout.numpy().copy(), pool8=P2.h_pool8.numpy().copy(),
+                   lowres_latents=P1.h_latout.numpy().copy(), unet_evals=(steps + hr_steps) * (2 if do_cfg else 1))
+        if want_float:
+            out["image"] = P2.img_f32.cpu().numpy()
+            out["upscaled_latents"] = P2.xk[0].cpu().numpy()
+        return out
+
+    @torch.inference_mode()
+    def generate(
+self, prompt_embeds, seeds, width, height, steps, guidance_scale=1.0, negative_embeds=None,
                  want_float=False, taps=None, latents=None, added=None, negative_added=None, noises=None, lane=0,
-                 strength=None, passes=0, start=None, control=None):
+                 strength=None, passes=0, start=None, control=None, hires=None):
         """prompt_embeds: [B,77,ctx] (any float dtype, host or device); seeds: B ints.  noises: optional per-request
         ``draw_noise(seed, h, w, steps - 1, init_noise_sigma)`` results drawn ahead by the callers (the worker's pool
         threads draw them in parallel, off the dispatcher's serial path); None: drawn here from the seeds.
@@ -397,8 +569,20 @@ class LcmHipPipeline:
         ControlNet of set_controlnet.  The scale is part of the plan key (the captured GEMMs carry it as a scalar argument);
         the hint is uploaded per request into the plan's fixed buffer.  Not combined with passes.  The result then carries
         ``controlnet_evals``.
+        hires = (W2, H2, hr_steps, strength, mode): hires fix -- ``generate_hires`` (its own RNG contract and result keys); not
+        combined with passes, control, latents or SDXL conditioning.
         Returns dict(rgb uint8 [B,H,W,3] (host), latents fp32 [B,4,h,w] (host), pool8 fp16 [B,4,8,8] (host))."""
         torch.cuda.set_device(self.device)        # the pool may call from a thread other than the constructing one
+        if hires is not None:
+            if passes or start is not None or (strength is not None and float(strength) != 1.0):
+                raise LcmHipError("hires fix is not combined with refinement passes")
+            if control is not None:
+                raise LcmHipError("hires fix is not combined with a ControlNet hint")
+            if latents is not None or added is not None or taps is not None:
+                raise LcmHipError("hires fix draws its noise from the seeds and is not served for SDXL: latents= / added= / taps= "
+                                  "are not supported")
+            return self.generate_hires(prompt_embeds, seeds, width, height, steps, hires, guidance_scale, negative_embeds,
+                                       want_float=want_float, noises=noises, lane=lane)
         pe = torch.as_tensor(prompt_embeds)
         B = pe.shape[0]
         check_size(width, height)
@@ -463,13 +647,7 @@ class LcmHipPipeline:
             if refine is not None and refine[2]:
                 for b in range(B):
                     P.xk[0, b].copy_(start[1][b].reshape(4, h, w), non_blocking=True)
-            pe16 = pe.to(torch.float16).reshape(B * TEXT_SEQ_LEN, -1)
-            if do_cfg:
-                ne16 = torch.as_tensor(negative_embeds).to(torch.float16).reshape(B * TEXT_SEQ_LEN, -1)
-                P.ehs[:B * TEXT_SEQ_LEN].copy_(ne16, non_blocking=True)
-                P.ehs[B * TEXT_SEQ_LEN:].copy_(pe16, non_blocking=True)
-            else:
-                P.ehs.copy_(pe16, non_blocking=True)
+            self._upload_text(P, pe, negative_embeds, guidance_scale)
             if self.unet.has_added:
                 def _add_rows(a):
                     pooled, tids = a
@@ -483,26 +661,13 @@ class LcmHipPipeline:
                     P.add_in[B:].copy_(rows, non_blocking=True)
                 else:
                     P.add_in.copy_(rows, non_blocking=True)
-            if has_cond:
-                gs = np.full((B,), float(guidance_scale) - 1.0, dtype=np.float32)
-                P.wemb.copy_(torch.from_numpy(guidance_scale_embedding(gs, P.wemb.shape[1])).to(torch.float16),
-                             non_blocking=True)
             # ---- the sampler: eager once (allocates scratch), then captured + replayed ----
             eager = (not self.use_graph) or taps is not None or want_float
             if eager:
                 with self._build_lock:               # eager launches allocate scratch
                     final = self._enqueue(P, guidance_scale, want_float=want_float, taps=taps)
             else:
-                if P.graph is None:
-                    with self._build_lock:
-                        if P.graph is None:
-                            self.tune(P)
-                            self._enqueue(P, guidance_scale)           # warm-up: allocates every scratch buffer
-                            stream.synchronize()
-                            g = ops.Graph()
-                            with g:
-                                self._enqueue(P, guidance_scale)
-                            P.graph = g
+                self._ensure_graph(P, guidance_scale)
                 P.graph.launch()
                 final = P.lat[B:] if do_cfg else P.lat
             P.h_rgb.copy_(P.rgb, non_blocking=True)
