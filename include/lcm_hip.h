@@ -165,6 +165,16 @@ int lcm_conv3x3_f16(const void* in, const void* W, const void* bias,
                     int B, int Hin, int Win, int Cin, int Cout, int stride, int ups,
                     void* stats_out, int64_t stats_bytes, int* slabs_per_image, void* stream);
 
+/* ---- AutoencoderKL encoder Downsample2D: F.pad(x, (0, 1, 0, 1)) -> 3x3 convolution, stride 2, padding 0 ----
+ * One zero row below / one zero column right of the image only: Ho = (Hin + 1 - 3) / 2 + 1, Wo likewise, and output (oy, ox)
+ * reads input rows 2 oy .. 2 oy + 2.  (lcm_conv3x3_f16 with stride 2 pads symmetrically and is another function.)
+ * in fp16 [B,Hin,Win,Cin], W fp16 [Cout][9][Cin], out fp16 [B,Ho,Wo,Cout]; bias only.  The row-gather implicit GEMM
+ * (csrc/vae_enc.hip): the canonical K partition of the per-image shape (lcm_canonical_splits, kind 1: Determinism, above), run
+ * as split launch + ordered reduce at every batch size; fused statistics per canonical 32-row slab as lcm_conv3x3_f16.
+ * Preconditions: Cin % 64 == 0, Cout % 64 == 0, Hin >= 2, Win >= 2. */
+int lcm_conv3x3_down_f16(const void* in, const void* W, const void* bias, void* out, int B, int Hin, int Win, int Cin, int Cout,
+                         void* stats_out, int64_t stats_bytes, int* slabs_per_image, void* stream);
+
 /* ---- fused GroupNorm(+SiLU) -> 3x3 convolution, stride 1 (ResnetBlock2D norm1->act->conv1, norm2->act->conv2) ----
  * LDS-halo implicit GEMM (csrc/conv_halo.hip).  Input = channel concat [in | in2] (in2 NULL: single source; fused
  * torch.cat of the skip).  gn_scale/gn_shift: fp32 [B][C1+C2] from lcm_groupnorm_affine_f16 (NULL: plain conv);
@@ -362,6 +372,20 @@ int lcm_scheduler_step_handover(const void* eps, const void* eps_uncond, float g
 #define LCM_UPSCALE_NEAREST_EXACT 2
 int lcm_latents_upscale_renoise(const void* x0, int h, int w, const void* noise, float sqrt_a, float sqrt_b, int mode, void* x_up,
                                 void* lat_out, int B, int H, int W, int dup, void* stream);
+
+/* ---- image-to-image: the two ends of the AutoencoderKL encoder (csrc/vae_enc.hip) ----
+ * lcm_vae_enc_conv_in_u8: encoder.conv_in from the picture.  in uint8 RGB [B,H,W,3]; x = 2 u8 / 255 - 1 is formed in the
+ *   kernel and carried as fp16 hi + lo (~22 bits); the zero padding applies to x (a border pixel's neighbours are 0, not -1).
+ *   W fp16 [Cout][9][3], out fp16 [B,H,W,Cout], Cout % 16 == 0 and <= 512; one fp32 chain per output, no K split; any H, W >= 1.
+ * lcm_vae_posterior_renoise: pre_mean / pre_logvar fp32 [B,h,w,4] (rows 0..3 / 4..7 of encoder.conv_out), quant_w fp32 [8][8],
+ *   quant_b fp32 [8], e0 / e1 fp32 [B,4,h,w].  moments = quant_w pre + quant_b (fp32);
+ *   z = (mean + exp(0.5 clamp(logvar, -30, 20)) e0) scaling_factor -> z_out fp32 [B,4,h,w];
+ *   lat_out = sqrt_a z + sqrt_b e1 (lcm_latents_renoise's expression); dup != 0: lat_out is [2B,4,h,w], both halves written;
+ *   moments_out: optional fp32 [B,8,h,w].  B*8*h*w < 2^30. */
+int lcm_vae_enc_conv_in_u8(const void* in, const void* W, const void* bias, void* out, int B, int H, int Wd, int Cout, void* stream);
+int lcm_vae_posterior_renoise(const void* pre_mean, const void* pre_logvar, const void* quant_w, const void* quant_b,
+                              const void* e0, const void* e1, float scaling_factor, float sqrt_a, float sqrt_b, void* z_out,
+                              void* lat_out, void* moments_out, int B, int h, int w, int dup, void* stream);
 
 /* ---- adaptive_avg_pool2d(lat,(8,8)) -> fp16 [B,4,8,8] (run_job_with_latents, backends/cuda_worker.py:299-304) */
 int lcm_latents_pool8(const void* lat, void* out_f16, int B, int h, int w, void* stream);

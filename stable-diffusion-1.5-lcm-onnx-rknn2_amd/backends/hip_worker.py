@@ -37,6 +37,7 @@ from ..scheduler import LCMSchedule
 from .. import weights as _weights
 from . import controlnet as _controlnet
 from . import hires as _hires
+from . import img2img as _img2img
 from . import refine as _refine
 
 
@@ -250,7 +251,7 @@ class _Engine:
         self.refine_cache = _refine.RefineCache(_refine.cache_bytes_from_env())
         self._stats_lock = threading.Lock()
         self.stats = dict(unet_evals=0, refine_cache_hits=0, refine_cache_misses=0, refine_cache_puts=0, controlnet_evals=0,
-                          hires_requests=0)
+                          hires_requests=0, img2img_requests=0)
         # ControlNet: where it comes from (CONTROLNET=<dir or file> | "synthetic" | None); loaded on the first request that
         # carries a hint, released with the pipeline
         self.controlnet_src = None
@@ -273,6 +274,16 @@ class _Engine:
             if pipe.controlnet is None:
                 sd, cfg = _controlnet.load_controlnet_source(self.controlnet_src, pipe.unet.cfg, self.synthetic_model)
                 pipe.set_controlnet(sd, cfg)
+
+    def ensure_vae_encoder(self):
+        """Build the VAE encoder on first use (image-to-image).  RuntimeError for a family that has none (SDXL) or a checkpoint
+        without encoder tensors."""
+        pipe = self.pipe
+        if pipe is None:
+            raise RuntimeError("worker engine is closed")
+        if not self.family_cls.IMG2IMG_OK:
+            raise RuntimeError("init_image: image-to-image is not served by the SDXL worker (SD1.5 and SD 2.x only)")
+        pipe.lane_vae_encoder(pipe.lanes[0])         # LcmHipError (a RuntimeError) when the checkpoint has no encoder
 
     # ---- style LoRAs (backends/cuda_worker.py:123-196) -----------------------------------------
     def _want_style(self, style_id, level):
@@ -358,6 +369,8 @@ class _Engine:
                         self.stats["controlnet_evals"] += steps
                 elif _hires.is_hires_key(key):
                     res = self._run_hires(pipe, key, items, noises, pe, kw, lane, stream)
+                elif _img2img.is_img2img_key(key):
+                    res = self._run_img2img(pipe, key, items, noises, pe, kw, lane, stream)
                 elif len(key) > 6:
                     res = self._run_refine(pipe, key, items, noises, pe, kw, lane, stream)
                 else:
@@ -418,14 +431,11 @@ class _Engine:
                 res[i] = (out["rgb"][b], out["pool8"][b:b + 1])
         return res
 
-    def _run_hires(self, pipe, key, items, noises, pe, kw, lane, stream):
-        """The passes of a hires batch (key = plain key + (KEY_TAG, target width, target height, hr_steps, strength, mode)).  The
-        second stage at a large target can need more split-K workspace than the lane has: the need is computed from the plan
-        and the batch runs as passes of the largest plan size that fits (bit-neutral: a request's bytes do not depend on its
-        batch) -- a request never fails on workspace a smaller pass would have served."""
-        width, height, steps, g = key[:4]
-        tw, th, hr_steps, strength, mode = key[7:12]
-        cap = pipe.hires_batch_cap(tw, th, hr_steps, strength, g, lane=lane, sizes=self.batch_sizes)
+    def _run_capped(self, items, noises, pe, kw, cap, stream, call):
+        """A batch as passes of at most ``cap`` items (the largest plan size whose split-K workspace need fits the lane: a
+        request never fails on workspace a smaller pass would have served; bit-neutral, a request's bytes do not depend on its
+        batch).  call(idx, sub_pe, sub_noises, sub_kw) -> the pipeline's result dict for the items ``idx``.
+        -> (per-item (rgb, pool8 row), UNet evaluations)."""
         n = len(items)
         res = [None] * n
 
@@ -442,15 +452,39 @@ class _Engine:
             with torch.cuda.stream(stream):          # the rows are gathered on the lane's stream, behind the text encoder
                 sub_pe = pe if whole else pe[idx]
                 sub_kw = kw if whole else {name: rows(v, idx) for name, v in kw.items()}
-            out = pipe.generate(sub_pe, [items[i][1] for i in idx], width, height, steps, g,
-                                noises=[noises[i] for i in idx] if noises is not None else None, lane=lane,
-                                hires=(tw, th, hr_steps, strength, mode), **sub_kw)
+            out = call(idx, sub_pe, [noises[i] for i in idx] if noises is not None else None, sub_kw)
             evals += out["unet_evals"]
             for b, i in enumerate(idx):
                 res[i] = (out["rgb"][b], out["pool8"][b:b + 1])
+        return res, evals
+
+    def _run_hires(self, pipe, key, items, noises, pe, kw, lane, stream):
+        """The passes of a hires batch (key = plain key + (KEY_TAG, target width, target height, hr_steps, strength, mode)).  The
+        second stage at a large target can need more split-K workspace than the lane has: the need is computed from the plan
+        and the batch runs as passes of the largest plan size that fits (_run_capped)."""
+        width, height, steps, g = key[:4]
+        tw, th, hr_steps, strength, mode = key[7:12]
+        cap = pipe.hires_batch_cap(tw, th, hr_steps, strength, g, lane=lane, sizes=self.batch_sizes)
+        res, evals = self._run_capped(items, noises, pe, kw, cap, stream, lambda idx, sub_pe, sub_noises, sub_kw: pipe.generate(
+            sub_pe, [items[i][1] for i in idx], width, height, steps, g, noises=sub_noises, lane=lane,
+            hires=(tw, th, hr_steps, strength, mode), **sub_kw))
         with self._stats_lock:
             self.stats["unet_evals"] += evals
             self.stats["hires_requests"] += len({id(it) for it in items})
+        return res
+
+    def _run_img2img(self, pipe, key, items, noises, pe, kw, lane, stream):
+        """The passes of an image-to-image batch (key = plain key + (KEY_TAG, strength); items carry the fitted picture), capped
+        like a hires batch -- by the workspace need of the strength-cut pass AND of the encoder stage (img2img_batch_cap)."""
+        width, height, steps, g = key[:4]
+        strength = key[7]
+        cap = pipe.img2img_batch_cap(width, height, steps, strength, g, lane=lane, sizes=self.batch_sizes)
+        res, evals = self._run_capped(items, noises, pe, kw, cap, stream, lambda idx, sub_pe, sub_noises, sub_kw: pipe.generate_img2img(
+            sub_pe, [items[i][1] for i in idx], np.stack([items[i][3] for i in idx]), width, height, steps, strength, g,
+            noises=sub_noises, lane=lane, **sub_kw))
+        with self._stats_lock:
+            self.stats["unet_evals"] += evals
+            self.stats["img2img_requests"] += len({id(it) for it in items})
         return res
 
     def start_batcher(self):
@@ -508,6 +542,7 @@ class HipLcmWorker:
 
     FAMILY = "sd15"
     CONTROLNET_OK = True
+    IMG2IMG_OK = True
 
     def __init__(self, worker_id: int, controlnet: str = None):
         """controlnet: a diffusers ControlNet directory or .safetensors file ("synthetic" with MODEL=synthetic*); None: the
@@ -598,6 +633,10 @@ class HipLcmWorker:
         eng = _Engine(type(self))
         eng.device = device
         eng.pipe = LcmHipPipeline(usd, vsd, ucfg, vcfg, device=device, schedule=sched)
+        if self.IMG2IMG_OK:
+            # the VAE encoder of image-to-image: where it comes from, nothing uploaded until a request carries a picture
+            # (synthetic weights are not even generated before that)
+            eng.pipe.set_vae_encoder_source(_weights.synthetic_vae_encoder if synthetic else getattr(vsd, "encoder", None), vcfg)
         with torch.cuda.stream(eng.pipe.stream):
             self._load_text_encoders(eng, device, ckpt_root, clip_sd, text_cfg)
         eng.refs = 1
@@ -715,6 +754,16 @@ class HipLcmWorker:
         rf = _refine.parse_refine(req)
         ctl = _controlnet.parse_control(req)
         hr = _hires.parse_hires(req, width, height, key[2])
+        i2i = _img2img.parse_img2img(req)
+        if i2i is not None:
+            # image-to-image jobs coalesce among themselves: the plain key + the strength (the picture is per image)
+            if hr is not None:
+                raise RuntimeError("init_image is not combined with enable_hr")
+            if rf is not None:
+                raise RuntimeError("init_image is not combined with refinement (denoise_strength < 1 or pass_number > 1)")
+            if ctl is not None:
+                raise RuntimeError("init_image is not combined with controlnet_image")
+            return key + (_img2img.KEY_TAG, i2i[0])
         if hr is not None:
             if rf is not None:
                 raise RuntimeError("enable_hr is not combined with refinement (denoise_strength < 1 or pass_number > 1)")
@@ -747,6 +796,14 @@ class HipLcmWorker:
             if key[0] % 8 == 0 and key[1] % 8 == 0 and key[0] > 0 and key[1] > 0 and key[2] >= 1:
                 noise = draw_noise(seed, key[1] // 8, key[0] // 8, n_draws - 1, eng.pipe.sched.init_noise_sigma)
             return (req, seed, noise, hint)
+        if _img2img.is_img2img_key(key):             # encoder on first use, the schedule's own error, the picture, the draws
+            eng.ensure_vae_encoder()
+            _img2img.check_schedule(eng.pipe.sched, key[2], key[7])
+            pic = _img2img.fit_init(_img2img.parse_img2img(req)[1], key[0], key[1])
+            if key[0] % 8 == 0 and key[1] % 8 == 0 and key[0] > 0 and key[1] > 0 and key[2] >= 1:
+                from ..pipeline import draw_noise_img2img
+                noise = draw_noise_img2img(seed, key[1] // 8, key[0] // 8, key[2])
+            return (req, seed, noise, pic)
         if _hires.is_hires_key(key):                 # the schedule's own error first, then the draws at both shapes
             tw, th, hr_steps, strength = key[7:11]
             _hires.check_schedule(eng.pipe.sched, hr_steps, strength)
@@ -987,6 +1044,7 @@ class HipLcmWorker:
 
 class HipLcmSDXLWorker(HipLcmWorker):
     CONTROLNET_OK = False        # a hint sent here raises for its job (SDXL ControlNets are out of scope)
+    IMG2IMG_OK = False           # so does a picture: the SDXL VAE's encoder is out of scope
     """SDXL worker (drop-in for DiffusersSDXLCudaWorker, backends/cuda_worker.py:307-614): two text encoders
     (CLIP-L hidden_states[-2] | OpenCLIP-bigG hidden_states[-2] -> 2048; pooled bigG text_embeds), size/crop time ids,
     classifier-free guidance when guidance_scale > 1 (negative conditioning = zeros, force_zeros_for_empty_prompt)."""
@@ -997,6 +1055,8 @@ class HipLcmSDXLWorker(HipLcmWorker):
     def _job_key(req):
         if getattr(req, "enable_hr", None):
             raise RuntimeError("enable_hr: hires fix is not served by the SDXL worker (SD1.5 and SD 2.x only)")
+        if getattr(req, "init_image", None) is not None or getattr(req, "init_images", None) is not None:
+            raise RuntimeError("init_image: image-to-image is not served by the SDXL worker (SD1.5 and SD 2.x only)")
         return HipLcmWorker._job_key(req)
 
     def _synthetic_weights(self):

@@ -650,46 +650,24 @@ def scale_vae_residual_stream(sd: dict, cfg: dict, s: float) -> dict:
 
 
 # ==================================================================================================
-class VAEDecoderHip(_Net):
-    def __init__(self, sd: dict, cfg: dict | None = None, device="cuda"):
-        super().__init__(device)
-        self.cfg = cfg = vae_config(cfg)
-        boc = cfg["block_out_channels"]
-        if float(cfg.get("residual_scale", 1.0)) != 1.0:
-            sd = scale_vae_residual_stream(sd, cfg, float(cfg["residual_scale"]))
-        self._put("pq.w", sd["post_quant_conv.weight"].reshape(4, 4), torch.float32)
-        self._put("pq.b", sd["post_quant_conv.bias"], torch.float32)
-        self._put("conv_in.w", pack_conv3x3(sd["decoder.conv_in.weight"]))
-        self._put("conv_in.b", sd["decoder.conv_in.bias"])
-        self._pack_resnet(sd, "decoder.mid_block.resnets.0")
-        self._pack_resnet(sd, "decoder.mid_block.resnets.1")
-        a = "decoder.mid_block.attentions.0"
+class _VAENet(_Net):
+    """What the AutoencoderKL decoder and encoder share: the mid block's single-head attention (weights ``attn.*``)."""
+
+    def _pack_mid_attention(self, sd, a, C):
         self._put("attn.norm.g", sd[a + ".group_norm.weight"])
         self._put("attn.norm.b", sd[a + ".group_norm.bias"])
         # the wide-head flash kernel is instantiated for d = 512 (every SD1.5 / SDXL AutoencoderKL); other widths take the
         # GEMM -> softmax -> transpose -> GEMM form
-        self.flash_attn = VAE_FLASH_ATTN and boc[-1] == 512
+        self.flash_attn = VAE_FLASH_ATTN and C == 512
         if self.flash_attn:
-            self._put("attn.qkv.w", torch.cat([sd[f"{a}.{n}.weight"].reshape(boc[-1], boc[-1]) for n in ("to_q", "to_k", "to_v")], 0))
+            self._put("attn.qkv.w", torch.cat([sd[f"{a}.{n}.weight"].reshape(C, C) for n in ("to_q", "to_k", "to_v")], 0))
             self._put("attn.qkv.b", torch.cat([sd[f"{a}.{n}.bias"] for n in ("to_q", "to_k", "to_v")], 0))
         else:
             for n in ("to_q", "to_k", "to_v"):
-                self._put(f"attn.{n}.w", sd[f"{a}.{n}.weight"].reshape(boc[-1], boc[-1]))
+                self._put(f"attn.{n}.w", sd[f"{a}.{n}.weight"].reshape(C, C))
                 self._put(f"attn.{n}.b", sd[f"{a}.{n}.bias"])
-        self._put("attn.o.w", sd[a + ".to_out.0.weight"].reshape(boc[-1], boc[-1]))
+        self._put("attn.o.w", sd[a + ".to_out.0.weight"].reshape(C, C))
         self._put("attn.o.b", sd[a + ".to_out.0.bias"])
-        nb = len(boc)
-        for i in range(nb):
-            for j in range(cfg["layers_per_block"] + 1):
-                self._pack_resnet(sd, f"decoder.up_blocks.{i}.resnets.{j}")
-            if i < nb - 1:
-                p = f"decoder.up_blocks.{i}.upsamplers.0.conv"
-                self._put(p + ".w", pack_conv3x3_up2(sd[p + ".weight"]))
-                self._put(p + ".b", sd[p + ".bias"])
-        self._put("norm_out.g", sd["decoder.conv_norm_out.weight"])
-        self._put("norm_out.b", sd["decoder.conv_norm_out.bias"])
-        self._put("conv_out.w", pack_conv3x3(sd["decoder.conv_out.weight"]))
-        self._put("conv_out.b", sd["decoder.conv_out.bias"])
 
     def mid_attention(self, x, C, B, H, W, x_st=None):
         w = self.w
@@ -728,6 +706,35 @@ class VAEDecoderHip(_Net):
         ops.gemm(sc, vt, o, M=S, N=C, K=Sp, lda=Sp, ldo=C, batch=B, strideA=S * Sp, strideW=C * Sp, strideO=S * C)
         ops.gemm(o, w["attn.o.w"], out, bias=w["attn.o.b"], res=x, stats=out_st, img_rows=S)
         return out, out_st
+
+
+# ==================================================================================================
+class VAEDecoderHip(_VAENet):
+    def __init__(self, sd: dict, cfg: dict | None = None, device="cuda"):
+        super().__init__(device)
+        self.cfg = cfg = vae_config(cfg)
+        boc = cfg["block_out_channels"]
+        if float(cfg.get("residual_scale", 1.0)) != 1.0:
+            sd = scale_vae_residual_stream(sd, cfg, float(cfg["residual_scale"]))
+        self._put("pq.w", sd["post_quant_conv.weight"].reshape(4, 4), torch.float32)
+        self._put("pq.b", sd["post_quant_conv.bias"], torch.float32)
+        self._put("conv_in.w", pack_conv3x3(sd["decoder.conv_in.weight"]))
+        self._put("conv_in.b", sd["decoder.conv_in.bias"])
+        self._pack_resnet(sd, "decoder.mid_block.resnets.0")
+        self._pack_resnet(sd, "decoder.mid_block.resnets.1")
+        self._pack_mid_attention(sd, "decoder.mid_block.attentions.0", boc[-1])
+        nb = len(boc)
+        for i in range(nb):
+            for j in range(cfg["layers_per_block"] + 1):
+                self._pack_resnet(sd, f"decoder.up_blocks.{i}.resnets.{j}")
+            if i < nb - 1:
+                p = f"decoder.up_blocks.{i}.upsamplers.0.conv"
+                self._put(p + ".w", pack_conv3x3_up2(sd[p + ".weight"]))
+                self._put(p + ".b", sd[p + ".bias"])
+        self._put("norm_out.g", sd["decoder.conv_norm_out.weight"])
+        self._put("norm_out.b", sd["decoder.conv_norm_out.bias"])
+        self._put("conv_out.w", pack_conv3x3(sd["decoder.conv_out.weight"]))
+        self._put("conv_out.b", sd["decoder.conv_out.bias"])
 
     def decode(self, lat, B, h, w_, rgb_out, img_f32=None, taps=None, use_tiling=True):
         """AutoencoderKL.decode with vae.enable_tiling() as the reference sets it (backends/cuda_worker.py:91): plain
@@ -810,3 +817,96 @@ class VAEDecoderHip(_Net):
         hn = self.buf.get("gn", B * H * W, ch)
         self._norm_conv_out(x, "norm_out", st, hn, rgb_out, B, H, W, ch, cfg["out_channels"], 1e-6, mode=1, out_f32=img_f32)
         return rgb_out
+
+
+# ==================================================================================================
+class VAEEncoderHip(_VAENet):
+    """AutoencoderKL.encode up to the pre-quant_conv moments, on the decoder's kernels plus three of its own: conv_in from the
+    uint8 picture (ops.vae_enc_conv_in_u8), Downsample2D with its bottom / right padding (ops.conv3x3_down) and -- issued by the
+    pipeline, because it also writes the sampler state -- quant_conv + posterior sample + re-noise (ops.vae_posterior_renoise).
+    fp16 storage, fp32 accumulation; no tiling at any size.  sd: the ``encoder.*`` and ``quant_conv.*`` tensors of the VAE."""
+
+    def __init__(self, sd: dict, cfg: dict | None = None, device="cuda"):
+        super().__init__(device)
+        self.cfg = cfg = vae_config(cfg)
+        boc = cfg["block_out_channels"]
+        if float(cfg.get("residual_scale", 1.0)) != 1.0:
+            raise ValueError("VAEEncoderHip: a VAE that needs residual scaling (force_upcast, the SDXL family) is not served")
+        if "encoder.conv_in.weight" not in sd or "quant_conv.weight" not in sd:
+            raise KeyError("this checkpoint carries no AutoencoderKL encoder (encoder.* / quant_conv.* tensors)")
+        lc = cfg["latent_channels"]
+        if lc != 4:
+            raise ValueError(f"VAEEncoderHip: latent_channels {lc} (the posterior launch is written for 4)")
+        self._put("conv_in.w", pack_conv3x3(sd["encoder.conv_in.weight"]))
+        self._put("conv_in.b", sd["encoder.conv_in.bias"])
+        nb = len(boc)
+        for i in range(nb):
+            for j in range(cfg["layers_per_block"]):
+                self._pack_resnet(sd, f"encoder.down_blocks.{i}.resnets.{j}")
+            if i < nb - 1:
+                p = f"encoder.down_blocks.{i}.downsamplers.0.conv"
+                self._put(p + ".w", pack_conv3x3(sd[p + ".weight"]))
+                self._put(p + ".b", sd[p + ".bias"])
+        self._pack_resnet(sd, "encoder.mid_block.resnets.0")
+        self._pack_resnet(sd, "encoder.mid_block.resnets.1")
+        self._pack_mid_attention(sd, "encoder.mid_block.attentions.0", boc[-1])
+        self._put("norm_out.g", sd["encoder.conv_norm_out.weight"])
+        self._put("norm_out.b", sd["encoder.conv_norm_out.bias"])
+        # conv_out has 2 x 4 output rows: the mean rows and the logvar rows, one conv3x3_smalln (Cout <= 4) launch each
+        wo, bo = sd["encoder.conv_out.weight"], sd["encoder.conv_out.bias"]
+        for n, r in (("mean", slice(0, lc)), ("logvar", slice(lc, 2 * lc))):
+            self._put(f"conv_out.{n}.w", pack_conv3x3(wo[r]))
+            self._put(f"conv_out.{n}.b", bo[r])
+        self._put("quant.w", sd["quant_conv.weight"].reshape(2 * lc, 2 * lc), torch.float32)
+        self._put("quant.b", sd["quant_conv.bias"], torch.float32)
+
+    def mid_block(self, x, ch, B, H, W, x_st=None):
+        x, st = self.resnet("encoder.mid_block.resnets.0", x, ch, ch, B, H, W, 1e-6, x_st=x_st)
+        x, st = self.mid_attention(x, ch, B, H, W, x_st=st)
+        return self.resnet("encoder.mid_block.resnets.1", x, ch, ch, B, H, W, 1e-6, out_role="cur", x_st=st)
+
+    def encode(self, img_u8, B, H, W, taps=None):
+        """img_u8 uint8 [B,H,W,3] -> (pre-quant_conv mean rows, logvar rows: fp32 [B,h,w,4] each, h, w)."""
+        cfg, wt = self.cfg, self.w
+        boc = cfg["block_out_channels"]
+        nb = len(boc)
+
+        def tap(name, t_, C, H_, W_):
+            if taps is not None:
+                taps[name] = t_.reshape(B, H_, W_, C).permute(0, 3, 1, 2).float().cpu()
+
+        ch = boc[0]
+        x = self.buf.get("enc_in", B * H * W, ch)
+        ops.vae_enc_conv_in_u8(img_u8, wt["conv_in.w"], x, B, H, W, ch, bias=wt["conv_in.b"])
+        tap("encoder.conv_in", x, ch, H, W)
+        st = None
+        roles = ("res_out", "cur")
+        for i in range(nb):
+            for j in range(cfg["layers_per_block"]):
+                p = f"encoder.down_blocks.{i}.resnets.{j}"
+                x, st = self.resnet(p, x, ch, boc[i], B, H, W, 1e-6, out_role=roles[j & 1], x_st=st)
+                ch = boc[i]
+                tap(p, x, ch, H, W)
+            if i < nb - 1:
+                p = f"encoder.down_blocks.{i}.downsamplers.0.conv"
+                Ho, Wo = (H - 2) // 2 + 1, (W - 2) // 2 + 1
+                y = self.buf.get("down", B * Ho * Wo, ch)
+                st = self.stats("down", B * Ho * Wo, ch, Ho * Wo)
+                ops.conv3x3_down(x, wt[p + ".w"], y, B, H, W, ch, ch, bias=wt[p + ".b"], stats=st)
+                H, W, x = Ho, Wo, y
+                tap(f"encoder.down_blocks.{i}.downsamplers.0", x, ch, H, W)
+        x, st = self.mid_block(x, ch, B, H, W, x_st=st)
+        tap("encoder.mid_block", x, ch, H, W)
+        pre_m = self.buf.get("pre_mean", B, H, W, 4, dtype=torch.float32)
+        pre_l = self.buf.get("pre_logvar", B, H, W, 4, dtype=torch.float32)
+        if st is not None and st.P > 0 and ch % 64 == 0:
+            sc_t, sh_t = ops.groupnorm_tables_from_stats(wt["norm_out.g"], wt["norm_out.b"], B, H * W, ch, st, self.gn_ws(B, H * W, ch), eps=1e-6)
+            for n, o in (("mean", pre_m), ("logvar", pre_l)):
+                ops.conv3x3_smalln(x, wt[f"conv_out.{n}.w"], o, B, H, W, ch, 4, bias=wt[f"conv_out.{n}.b"], mode=0,
+                                   gn_scale=sc_t, gn_shift=sh_t, silu=True)
+        else:
+            hn = self.buf.get("gn", B * H * W, ch)
+            self.norm(x, wt["norm_out.g"], wt["norm_out.b"], hn, B, H * W, ch, x_st=st, eps=1e-6)
+            for n, o in (("mean", pre_m), ("logvar", pre_l)):
+                ops.conv3x3_smalln(hn, wt[f"conv_out.{n}.w"], o, B, H, W, ch, 4, bias=wt[f"conv_out.{n}.b"], mode=0)
+        return pre_m, pre_l, H, W

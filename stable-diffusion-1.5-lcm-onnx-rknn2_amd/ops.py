@@ -246,6 +246,27 @@ def conv3x3(x, w, out, B, H, W, Cin, Cout, *, bias=None, rowadd=None, res=None, 
     return out
 
 
+def conv3x3_down(x, w, out, B, H, W, Cin, Cout, *, bias=None, stats=None):
+    """The AutoencoderKL encoder's Downsample2D: F.pad(x, (0, 1, 0, 1)) -> conv3x3(stride 2, padding 0), x fp16 [B*H*W, Cin] ->
+    out fp16 [B*Ho*Wo, Cout] with Ho = (H - 2) // 2 + 1 (include/lcm_hip.h, lcm_conv3x3_down_f16).  Recorded as a kind-1
+    contraction like the stride-2 conv3x3: the same canonical K partition (``splittable``, ``m_img``) and statistics."""
+    L = _lib.load()
+    sbuf, sbytes, sp = _stats_args(stats)
+    Ho, Wo = (H - 2) // 2 + 1, (W - 2) // 2 + 1
+    Mo = B * Ho * Wo
+    RECORD = _record_list()
+    if RECORD is not None:
+        RECORD.append(((1, Mo, Cout, 9 * Cin, 1), dict(halo=False, W=Wo, phases=1, m_img=Mo // B, splittable=True),
+                       lambda: conv3x3_down(x, w, out, B, H, W, Cin, Cout, bias=bias, stats=stats)))
+    with _Timed("conv3x3", 2.0 * Mo * Cout * 9 * Cin, 2.0 * (B * H * W * Cin + 9 * Cin * Cout + Mo * Cout)):
+        rc = L.lcm_conv3x3_down_f16(_p(x), _p(w), _p(bias), _p(out), B, H, W, Cin, Cout, sbuf, sbytes,
+                                    C.byref(sp) if sp is not None else None, _stream())
+    if stats is not None:
+        stats.P = sp.value
+    _lib.check(rc, "lcm_conv3x3_down_f16")
+    return out
+
+
 def conv3x3_gn(x, w, out, B, H, W, C1, Cout, *, x2=None, C2=0, gn_scale=None, gn_shift=None, silu=True, bias=None,
                rowadd=None, res=None, ups=0, stats=None):
     """Fused [GroupNorm-apply (+SiLU)] -> conv3x3 (stride 1) over the channel concat [x | x2]."""
@@ -316,6 +337,25 @@ def hint_conv_u8(img_u8, w, out, B, H, W, Cout, *, bias=None, silu=True):
     L = _lib.load()
     _lib.check(L.lcm_hint_conv_u8(_p(img_u8), _p(w), _p(bias), _p(out), B, H, W, Cout, 1 if silu else 0, _stream()), "lcm_hint_conv_u8")
     return out
+
+
+def vae_enc_conv_in_u8(img_u8, w, out, B, H, W, Cout, *, bias=None):
+    """AutoencoderKL encoder conv_in from the uploaded picture: uint8 RGB [B,H,W,3] -> fp16 [B*H*W, Cout], 2 x / 255 - 1 applied
+    in the kernel, zero padding after it (include/lcm_hip.h, lcm_vae_enc_conv_in_u8).  w: fp16 [Cout][27] (packing.pack_conv3x3)."""
+    L = _lib.load()
+    _lib.check(L.lcm_vae_enc_conv_in_u8(_p(img_u8), _p(w), _p(bias), _p(out), B, H, W, Cout, _stream()), "lcm_vae_enc_conv_in_u8")
+    return out
+
+
+def vae_posterior_renoise(pre_mean, pre_logvar, quant_w, quant_b, e0, e1, scaling, sqrt_a, sqrt_b, z_out, lat, B, h, w, *,
+                          moments=None, dup=False):
+    """quant_conv -> posterior sample (e0) -> x scaling -> re-noise (e1) in one launch: z_out fp32 [B,4,h,w] <- the clean latents,
+    lat <- sqrt_a z + sqrt_b e1 (dup: both halves of [2B,4,h,w]); moments: optional fp32 [B,8,h,w] (lcm_vae_posterior_renoise)."""
+    L = _lib.load()
+    _lib.check(L.lcm_vae_posterior_renoise(_p(pre_mean), _p(pre_logvar), _p(quant_w), _p(quant_b), _p(e0), _p(e1), float(scaling),
+                                           float(sqrt_a), float(sqrt_b), _p(z_out), _p(lat), _p(moments), int(B), int(h), int(w),
+                                           int(bool(dup)), _stream()), "lcm_vae_posterior_renoise")
+    return lat
 
 
 def hint_conv(x, w, out, B, H, W, Cin, Cout, *, bias=None, stride=1, silu=True):

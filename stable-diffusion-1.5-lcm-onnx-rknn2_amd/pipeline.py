@@ -25,7 +25,7 @@ import torch
 from . import ops
 from .config import TEXT_SEQ_LEN, VAE_SCALE_FACTOR
 from .lib import LcmHipError
-from .model import ControlNetHip, UNetHip, VAEDecoderHip
+from .model import ControlNetHip, UNetHip, VAEDecoderHip, VAEEncoderHip
 from .scheduler import LCMSchedule
 
 
@@ -74,6 +74,17 @@ def draw_noise_hires(seed: int, h: int, w: int, steps: int, h2: int, w2: int, hr
     return lat, lo, hi
 
 
+def draw_noise_img2img(seed: int, h: int, w: int, steps: int, sigma: float = 1.0):
+    """An image-to-image request's RNG stream, all from its one seeded generator and in this order: e0, the posterior sample's
+    draw; e1, the re-noise draw at the first timestep of the strength-cut schedule; then the steps - 1 step noises
+    -> (e0, [e1, e2, ...]) (``steps`` tensors in the list), each fp32 [1,4,h,w].  ``sigma`` is accepted for symmetry with
+    ``draw_noise`` and unused: neither draw is an initial latent, so nothing is multiplied by init_noise_sigma."""
+    g = torch.Generator(device="cpu").manual_seed(int(seed))
+    e0 = torch.randn((1, 4, h, w), generator=g, dtype=torch.float32)
+    rest = [torch.randn((1, 4, h, w), generator=g, dtype=torch.float32) for _ in range(int(steps))]
+    return e0, rest
+
+
 _DEFAULT_WS = {}
 
 
@@ -112,6 +123,8 @@ class _Lane:
         ops.set_stream_workspace(self.stream, self.splitk_ws)
         self.controlnet = None        # this lane's executor of the pipeline's ControlNet (LcmHipPipeline.lane_controlnet)
         self._controlnet_of = None
+        self.vae_enc = None           # this lane's executor of the VAE encoder (LcmHipPipeline.lane_vae_encoder)
+        self.enc_plans = {}           # (B, H, W) -> _EncPlan: the encoder stage of image-to-image requests
 
 
 class _Plan:
@@ -172,6 +185,25 @@ class _Plan:
         self.h_latout = torch.zeros(B, 4, h, w, dtype=torch.float32).pin_memory()
 
 
+class _EncPlan:
+    """The encoder stage of image-to-image requests of one (lane, B, H, W): the picture's fixed device buffer, the posterior
+    sample's noise, and the captured graph of VAEEncoderHip.encode (its outputs live in the lane executor's scratch)."""
+
+    def __init__(self, pipe, lane, B, H, W):
+        dev = pipe.device
+        h, w = H // VAE_SCALE_FACTOR, W // VAE_SCALE_FACTOR
+        self.B, self.H, self.W = B, H, W
+        with torch.cuda.stream(lane.stream):
+            self.img = torch.zeros(B, H, W, 3, dtype=torch.uint8, device=dev)
+            self.e0 = torch.zeros(B, 4, h, w, dtype=torch.float32, device=dev)
+            self.moments = torch.zeros(B, 8, h, w, dtype=torch.float32, device=dev)
+        self.h_img = torch.zeros(B, H, W, 3, dtype=torch.uint8).pin_memory()
+        self.h_e0 = torch.zeros(B, 4, h, w, dtype=torch.float32).pin_memory()
+        self.h_z = torch.zeros(B, 4, h, w, dtype=torch.float32).pin_memory()
+        self.graph = None
+        self.pre = None               # (pre_mean, pre_logvar): set by the first eager run, the same tensors ever after
+
+
 class LcmHipPipeline:
     def __init__(self, unet_sd, vae_sd, unet_cfg=None, vae_cfg=None, device="cuda:0", schedule: LCMSchedule | None = None,
                  use_graph=True):
@@ -187,6 +219,8 @@ class LcmHipPipeline:
         self._tuned_keys = set()
         self._build_lock = threading.RLock()      # tuning / eager warm-up / capture of a plan: one lane at a time
         self.controlnet = None
+        self.vae_encoder = None                   # VAEEncoderHip, built on the first image-to-image request
+        self.vae_encoder_src = None               # (host state dict with encoder.* / quant_conv.*, VAE config) or None
         self.lanes = [_Lane(self, 0, self.unet, self.vae)]
         self.stream = self.lanes[0].stream
         self._plans = self.lanes[0].plans
@@ -236,6 +270,133 @@ class LcmHipPipeline:
             L.controlnet = self.controlnet if L.index == 0 else self.controlnet.view()
             L._controlnet_of = self.controlnet
         return L.controlnet
+
+    def set_vae_encoder_source(self, sd, cfg=None):
+        """Where the VAE encoder comes from: the ``encoder.*`` / ``quant_conv.*`` tensors of the checkpoint (host) and its VAE
+        config.  Nothing is uploaded until an image-to-image request arrives."""
+        self.vae_encoder_src = (sd, cfg) if sd else None
+
+    def lane_vae_encoder(self, L: _Lane):
+        """The lane's executor of the VAE encoder, built (and uploaded) on first use: weights shared, scratch per lane."""
+        if self.vae_encoder is None:
+            with self._build_lock:
+                if self.vae_encoder is None:
+                    if not self.vae_encoder_src:
+                        raise LcmHipError("init_image: this checkpoint carries no VAE encoder (encoder.* / quant_conv.* tensors)")
+                    sd, cfg = self.vae_encoder_src
+                    sd = sd() if callable(sd) else sd
+                    if not sd or "encoder.conv_in.weight" not in sd or "quant_conv.weight" not in sd:
+                        raise LcmHipError("init_image: this checkpoint carries no VAE encoder (encoder.* / quant_conv.* tensors)")
+                    from .weights import audit_vae_encoder
+                    sd = audit_vae_encoder(sd, cfg if cfg is not None else self.vae.cfg)
+                    with torch.cuda.stream(self.stream):
+                        self.vae_encoder = VAEEncoderHip(sd, cfg if cfg is not None else self.vae.cfg, self.device)
+                        self.stream.synchronize()
+        if L.vae_enc is None:
+            L.vae_enc = self.vae_encoder if L.index == 0 else self.vae_encoder.view()
+        return L.vae_enc
+
+    def _enc_plan(self, L: _Lane, B, H, W) -> _EncPlan:
+        E = L.enc_plans.get((B, H, W))
+        if E is None:
+            with self._build_lock:
+                E = L.enc_plans.get((B, H, W))
+                if E is None:
+                    E = L.enc_plans[(B, H, W)] = _EncPlan(self, L, B, H, W)
+        return E
+
+    def _encode_stage(self, L: _Lane, E: _EncPlan, eager: bool):
+        """VAEEncoderHip.encode of E.img on the current (the lane's) stream -> (pre_mean, pre_logvar).  The stage is a captured
+        graph of its own per (lane, B, H, W) -- ~120 launches that depend on nothing but the picture, replayed like the sampler's;
+        the first use runs it eagerly once (allocates the executor's scratch), then captures.  eager: plain launches."""
+        enc = self.lane_vae_encoder(L)
+        if eager or E.graph is None:
+            with self._build_lock:
+                pm, pl, h, w = enc.encode(E.img, E.B, E.H, E.W)
+                E.pre = (pm, pl)
+                if not eager and E.graph is None:
+                    L.stream.synchronize()
+                    g = ops.Graph()
+                    with g:
+                        enc.encode(E.img, E.B, E.H, E.W)
+                    E.graph = g
+            return E.pre
+        E.graph.launch()
+        return E.pre
+
+    @torch.inference_mode()
+    def generate_img2img(self, prompt_embeds, seeds, images_u8, width, height, steps, strength, guidance_scale=1.0,
+                         negative_embeds=None, want_float=False, noises=None, lane=0):
+        """Image-to-image with the semantics of diffusers' LatentConsistencyModelImg2ImgPipeline: images_u8 uint8 [B,H,W,3] at the
+        request's size -> AutoencoderKL encoder -> z = (mean + exp(0.5 clamp(logvar, -30, 20)) e0) scaling_factor -> re-noised to
+        the first timestep of ``timesteps(steps, strength)`` with e1 -> ``steps`` LCM steps over that schedule -> decode.  On the
+        lane's stream, nothing copied to the host in between: the encoder stage (its own captured graph; eager with want_float or
+        use_graph=False), lcm_vae_posterior_renoise into the state of the "from-state" plan, that plan.  noises: optional
+        per-request ``draw_noise_img2img`` results.  Returns the usual dict plus ``init_latents`` (host fp32 [B,4,h,w]: z) and
+        ``unet_evals`` = steps (doubled under classifier-free guidance); with want_float also ``image`` and ``moments`` (host fp32
+        [B,8,h,w]: the posterior's mean | logvar)."""
+        torch.cuda.set_device(self.device)
+        pe = torch.as_tensor(prompt_embeds)
+        B = pe.shape[0]
+        steps, strength = int(steps), float(strength)
+        check_size(width, height)
+        if self.unet.has_added:
+            raise LcmHipError("image-to-image is not served for SDXL-family UNets")
+        if not 0.0 < strength <= 1.0:
+            raise LcmHipError(f"image-to-image strength {strength} outside (0, 1]")
+        img = torch.as_tensor(images_u8)
+        if img.dtype != torch.uint8 or tuple(img.shape) != (B, height, width, 3):
+            raise LcmHipError(f"init images must be uint8 [B={B}, H={height}, W={width}, 3], got {img.dtype} {tuple(img.shape)}")
+        do_cfg = (guidance_scale > 1.0) and not self.unet.has_cond
+        if do_cfg and negative_embeds is None:
+            raise LcmHipError("classifier-free guidance needs negative_embeds")
+        ts = self.sched.timesteps(steps, strength)       # diffusers' error for steps > original_steps x strength, before any plan
+        nsa, nsb = self.sched.renoise_coefficients(ts[0])
+        h, w = height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR
+        P = self.plan(B, h, w, steps, do_cfg, guidance_scale, lane=lane, refine=(strength, 1, True), kind="from-state")
+        L = P.lane
+        self.lane_vae_encoder(L)                         # raises for a checkpoint without an encoder, before anything is queued
+        E = self._enc_plan(L, B, height, width)
+        stream = L.stream
+        with torch.cuda.stream(stream):
+            for b, s in enumerate(seeds):
+                e0, rest = noises[b] if noises is not None else draw_noise_img2img(s, h, w, steps)
+                if len(rest) != steps:
+                    raise LcmHipError(f"request {b}: 1 + {len(rest)} noise tensors drawn ahead, the chain needs 1 + {steps}")
+                E.h_e0[b].copy_(e0[0])
+                for i, n in enumerate(rest):
+                    P.h_noise[i, b].copy_(n[0])
+            E.h_img.copy_(img)
+            eager = (not self.use_graph) or want_float
+            if not eager:                            # the sampler's graph first: its warm-up pass overwrites the plan's state
+                self._ensure_graph(P, guidance_scale)
+            E.img.copy_(E.h_img, non_blocking=True)
+            E.e0.copy_(E.h_e0, non_blocking=True)
+            P.noise.copy_(P.h_noise, non_blocking=True)
+            self._upload_text(P, pe, negative_embeds, guidance_scale)
+            # ---- encoder -> hand-over -> the strength-cut pass, in stream order ----
+            pre_m, pre_l = self._encode_stage(L, E, eager)
+            enc = L.vae_enc
+            ops.vae_posterior_renoise(pre_m, pre_l, enc.w["quant.w"], enc.w["quant.b"], E.e0, P.noise[0],
+                                      self.vae.cfg["scaling_factor"], nsa, nsb, P.xk[0], P.lat, B, h, w,
+                                      moments=E.moments if want_float else None, dup=do_cfg)
+            if eager:
+                with self._build_lock:
+                    self._enqueue(P, guidance_scale, want_float=want_float)
+            else:
+                P.graph.launch()
+            final = P.lat[B:] if do_cfg else P.lat
+            P.h_rgb.copy_(P.rgb, non_blocking=True)
+            P.h_pool8.copy_(P.pool8, non_blocking=True)
+            P.h_latout.copy_(final, non_blocking=True)
+            E.h_z.copy_(P.xk[0], non_blocking=True)
+            stream.synchronize()
+        out = dict(rgb=P.h_rgb.numpy().copy(), latents=P.h_latout.numpy().copy(), pool8=P.h_pool8.numpy().copy(),
+                   init_latents=E.h_z.numpy().copy(), unet_evals=steps * (2 if do_cfg else 1))
+        if want_float:
+            out["image"] = P.img_f32.cpu().numpy()
+            out["moments"] = E.moments.cpu().numpy()
+        return out
 
     def _enqueue(self, P: _Plan, guidance: float, want_float=False, taps=None):
         """Enqueue the whole sampler on the current stream (this is what gets captured): a chain of passes, each the LCM steps
@@ -375,6 +536,10 @@ class LcmHipPipeline:
                 if P.graph is not None:
                     P.graph.close()
             L.plans.clear()
+            for E in L.enc_plans.values():
+                if E.graph is not None:
+                    E.graph.close()
+            L.enc_plans.clear()
 
     def close(self):
         """Drop the captured graphs and take this pipeline's workspaces out of the library's per-stream table (the library
@@ -386,6 +551,10 @@ class LcmHipPipeline:
                 if P.graph is not None:
                     P.graph.close()
             L.plans.clear()
+            for E in getattr(L, "enc_plans", {}).values():
+                if E.graph is not None:
+                    E.graph.close()
+            getattr(L, "enc_plans", {}).clear()
             try:
                 torch.cuda.synchronize(self.device)
                 ops.set_stream_workspace(L.stream, L.splitk_ws, forget=True)      # only if the entry is still this lane's
@@ -440,21 +609,55 @@ class LcmHipPipeline:
             raise LcmHipError("splitk_need: a batch-1 plan, please")
         need = getattr(P, "_splitk_need", None)
         if need is None:
-            from . import autotune
             with self._build_lock, torch.cuda.stream(P.lane.stream):
                 with ops.recording() as recs:
                     self._enqueue(P, 1.0)
                 P.lane.stream.synchronize()
-            need = 0
-            for key, meta, _ in recs:
-                if key is None or not meta.get("splittable"):
-                    continue
-                m_img = meta.get("m_img", key[1])
-                sp = autotune._canonical_splits(key, meta, m_img)
-                if sp > 1:
-                    need = max(need, 4 * sp * m_img * key[2])
-            P._splitk_need = need
+            need = P._splitk_need = self._need_of(recs)
         return need
+
+    @staticmethod
+    def _need_of(recs) -> int:
+        """The largest fp32 slab set (bytes per image) among recorded launches: parts x rows per image x N x 4 of every
+        splittable contraction whose canonical K partition has parts."""
+        from . import autotune
+        need = 0
+        for key, meta, _ in recs:
+            if key is None or not meta.get("splittable"):
+                continue
+            m_img = meta.get("m_img", key[1])
+            sp = autotune._canonical_splits(key, meta, m_img)
+            if sp > 1:
+                need = max(need, 4 * sp * m_img * key[2])
+        return need
+
+    def encoder_splitk_need(self, width, height, lane=0) -> int:
+        """splitk_need of the VAE encoder stage at width x height, per picture: one eager batch-1 encode is recorded.  The
+        encoder's Downsample2D runs its canonical partition as split launch + reduce at every batch, so a batch of n needs n
+        times this."""
+        L = self.lane(lane)
+        E = self._enc_plan(L, 1, height, width)
+        need = getattr(E, "_splitk_need", None)
+        if need is None:
+            enc = self.lane_vae_encoder(L)
+            with self._build_lock, torch.cuda.stream(L.stream):
+                with ops.recording() as recs:
+                    enc.encode(E.img, 1, height, width)
+                L.stream.synchronize()
+            need = E._splitk_need = self._need_of(recs)
+        return need
+
+    def img2img_batch_cap(self, width, height, steps, strength, guidance_scale=1.0, lane=0, sizes=(1, 2, 4, 8)) -> int:
+        """The largest pass size of ``sizes`` at which BOTH stages of an image-to-image request at width x height fit the lane's
+        split-K workspace: the strength-cut pass (hires_batch_cap's count, doubled rows under classifier-free guidance) and the
+        encoder stage.  The stages run one after the other on one stream, so the need is the larger of the two."""
+        do_cfg = (guidance_scale > 1.0) and not self.unet.has_cond
+        P = self.plan(1, height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR, int(steps), do_cfg, guidance_scale, lane=lane,
+                      refine=(float(strength), 1, True), kind="from-state")
+        per_request = max(self.splitk_need(P) * (2 if do_cfg else 1), self.encoder_splitk_need(width, height, lane))
+        have = P.lane.splitk_ws.numel() * 4
+        fit = [n for n in sorted(sizes) if n * per_request <= have]
+        return fit[-1] if fit else min(sizes)
 
     def hires_batch_cap(self, width, height, hr_steps, strength, guidance_scale=1.0, lane=0, sizes=(1, 2, 4, 8)) -> int:
         """The largest pass size of ``sizes`` whose second stage at width x height fits the lane's split-K workspace (at least

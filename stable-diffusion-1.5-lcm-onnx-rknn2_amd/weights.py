@@ -151,6 +151,40 @@ def vae_param_spec(cfg: dict | None = None):
     yield "decoder.conv_out.bias", (cfg["out_channels"],), "bias"
 
 
+def vae_encoder_param_spec(cfg: dict | None = None):
+    """The encoder side of AutoencoderKL (diffusers ``Encoder`` + ``quant_conv``): what image-to-image needs beside the decoder."""
+    cfg = vae_config(cfg)
+    boc = cfg["block_out_channels"]
+    lc = cfg["latent_channels"]
+    yield "encoder.conv_in.weight", (boc[0], cfg.get("in_channels", 3), 3, 3), "w"
+    yield "encoder.conv_in.bias", (boc[0],), "bias"
+    ch = boc[0]
+    nb = len(boc)
+    for i in range(nb):
+        for j in range(cfg["layers_per_block"]):
+            yield from _resnet(f"encoder.down_blocks.{i}.resnets.{j}", ch, boc[i], 0)
+            ch = boc[i]
+        if i < nb - 1:
+            yield f"encoder.down_blocks.{i}.downsamplers.0.conv.weight", (ch, ch, 3, 3), "w"
+            yield f"encoder.down_blocks.{i}.downsamplers.0.conv.bias", (ch,), "bias"
+    yield from _resnet("encoder.mid_block.resnets.0", ch, ch, 0)
+    a = "encoder.mid_block.attentions.0"
+    yield a + ".group_norm.weight", (ch,), "gamma"
+    yield a + ".group_norm.bias", (ch,), "beta"
+    for n in ("to_q", "to_k", "to_v"):
+        yield f"{a}.{n}.weight", (ch, ch), "w"
+        yield f"{a}.{n}.bias", (ch,), "bias"
+    yield a + ".to_out.0.weight", (ch, ch), "w_res"
+    yield a + ".to_out.0.bias", (ch,), "bias"
+    yield from _resnet("encoder.mid_block.resnets.1", ch, ch, 0)
+    yield "encoder.conv_norm_out.weight", (ch,), "gamma"
+    yield "encoder.conv_norm_out.bias", (ch,), "beta"
+    yield "encoder.conv_out.weight", (2 * lc, ch, 3, 3), "w_out"
+    yield "encoder.conv_out.bias", (2 * lc,), "bias"
+    yield "quant_conv.weight", (2 * lc, 2 * lc, 1, 1), "w"
+    yield "quant_conv.bias", (2 * lc,), "bias"
+
+
 def count_params(spec) -> int:
     n = 0
     for _, shape, _ in spec:
@@ -200,6 +234,29 @@ def synthetic_sd2_unet(seed=0):
 
 def synthetic_vae(cfg=None, seed=1):
     return synthetic_state_dict(vae_param_spec(cfg), seed)
+
+
+def synthetic_vae_encoder(cfg=None, seed=4):
+    """Seeded synthetic ``encoder.*`` / ``quant_conv.*`` tensors: a generator of its own, so ``synthetic_vae`` keeps its bits."""
+    return synthetic_state_dict(vae_encoder_param_spec(cfg), seed)
+
+
+def has_vae_encoder(vsd: dict) -> bool:
+    return "encoder.conv_in.weight" in vsd and "quant_conv.weight" in vsd
+
+
+def audit_vae_encoder(vsd: dict, vcfg) -> dict:
+    """The encoder tensors of a loaded VAE state dict, checked against the graph -> {name: tensor}.  RuntimeError if the
+    checkpoint carries none or they do not fit."""
+    if not has_vae_encoder(vsd):
+        raise RuntimeError("init_image: this checkpoint carries no VAE encoder (encoder.* / quant_conv.* tensors)")
+    out = {}
+    for name, shape, _ in vae_encoder_param_spec(vcfg):
+        if name not in vsd:
+            raise RuntimeError(f"checkpoint/graph mismatch at vae '{name}': missing")
+        t = vsd[name]
+        out[name] = t if tuple(t.shape) == tuple(shape) else t.reshape(shape)     # linear attn stored as 1x1 conv or vice versa
+    return out
 
 
 # ---------------------------------------------------------------------------------------
@@ -399,6 +456,22 @@ def _load_safetensors_dir(d: str) -> dict:
     raise FileNotFoundError(f"no diffusion_pytorch_model*.safetensors under {d}")
 
 
+class VaeStateDict(dict):
+    """The decoder side of an AutoencoderKL checkpoint (``decoder.*``, ``post_quant_conv.*``: what every request needs), with the
+    encoder side of the same checkpoint beside it: ``.encoder`` = {``encoder.*`` / ``quant_conv.*``: host tensor}, empty when the
+    checkpoint has none.  It stays on the host until an image-to-image request asks for it (model.VAEEncoderHip, built lazily)."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.encoder = {}
+
+
+def split_vae_encoder(vsd: dict) -> VaeStateDict:
+    out = VaeStateDict((k, v) for k, v in vsd.items() if k.startswith("decoder.") or k.startswith("post_quant_conv."))
+    out.encoder = {k: v for k, v in vsd.items() if k.startswith("encoder.") or k.startswith("quant_conv.")}
+    return out
+
+
 def load_diffusers_dir(root: str):
     """-> (unet_sd, unet_cfg, vae_sd, vae_cfg) from a diffusers-layout checkpoint directory."""
     def cfg_of(sub, base):
@@ -421,7 +494,7 @@ def load_diffusers_dir(root: str):
     _, vcfg = cfg_of("vae", vae_config())
     usd = _load_safetensors_dir(os.path.join(root, "unet"))
     vsd = _load_safetensors_dir(os.path.join(root, "vae"))
-    vsd = {k: v for k, v in vsd.items() if k.startswith("decoder.") or k.startswith("post_quant_conv.")}
+    vsd = split_vae_encoder(vsd)
     # older VAE checkpoints name the mid attention query/key/value/proj_attn
     ren = {"query": "to_q", "key": "to_k", "value": "to_v", "proj_attn": "to_out.0"}
     for k in list(vsd):
@@ -429,6 +502,11 @@ def load_diffusers_dir(root: str):
             tag = f".attentions.0.{old}."
             if tag in k:
                 vsd[k.replace(tag, f".attentions.0.{new}.")] = vsd.pop(k)
+    for k in list(vsd.encoder):
+        for old, new in ren.items():
+            tag = f".attentions.0.{old}."
+            if tag in k:
+                vsd.encoder[k.replace(tag, f".attentions.0.{new}.")] = vsd.encoder.pop(k)
     for name, shape, _ in list(unet_param_spec(ucfg)) :
         if name not in usd or tuple(usd[name].shape) != tuple(shape):
             raise RuntimeError(f"checkpoint/graph mismatch at unet '{name}': expected {shape}, "
@@ -495,28 +573,54 @@ def _ldm_unet_key(k: str, layers_per_block: int = 2, down_attn=(True, True, True
 
 
 def _ldm_vae_key(k: str, n_up: int = 4):
-    """'first_stage_model.' key (prefix stripped) -> diffusers AutoencoderKL key (decoder side only)."""
-    if k.startswith("post_quant_conv."):
+    """'first_stage_model.' key (prefix stripped) -> diffusers AutoencoderKL key, decoder and encoder side (None to drop)."""
+    if k.startswith("post_quant_conv.") or k.startswith("quant_conv."):
         return k
-    if not k.startswith("decoder."):
+    side = k.split(".")[0]
+    if side not in ("decoder", "encoder"):
         return None
     p = k.split(".")[1:]
     ren = {"nin_shortcut": "conv_shortcut"}
     if p[0] in ("conv_in", "conv_out"):
-        return "decoder." + ".".join(p)
+        return side + "." + ".".join(p)
     if p[0] == "norm_out":
-        return "decoder.conv_norm_out." + p[1]
+        return side + ".conv_norm_out." + p[1]
     if p[0] == "mid":
         if p[1].startswith("block_"):
-            return f"decoder.mid_block.resnets.{int(p[1][-1]) - 1}." + ".".join(ren.get(t, t) for t in p[2:])
+            return f"{side}.mid_block.resnets.{int(p[1][-1]) - 1}." + ".".join(ren.get(t, t) for t in p[2:])
         a = {"norm": "group_norm", "q": "to_q", "k": "to_k", "v": "to_v", "proj_out": "to_out.0"}[p[2]]
-        return f"decoder.mid_block.attentions.0.{a}." + p[3]
-    if p[0] == "up":
+        return f"{side}.mid_block.attentions.0.{a}." + p[3]
+    if p[0] == "up" and side == "decoder":
         b = n_up - 1 - int(p[1])
         if p[2] == "block":
             return f"decoder.up_blocks.{b}.resnets.{p[3]}." + ".".join(ren.get(t, t) for t in p[4:])
         return f"decoder.up_blocks.{b}.upsamplers.0.conv." + p[-1]
+    if p[0] == "down" and side == "encoder":                 # down.{i}.block.{j}.* / down.{i}.downsample.conv.*
+        if p[2] == "block":
+            return f"encoder.down_blocks.{p[1]}.resnets.{p[3]}." + ".".join(ren.get(t, t) for t in p[4:])
+        return f"encoder.down_blocks.{p[1]}.downsamplers.0.conv." + p[-1]
     return None
+
+
+def ldm_vae_encoder_key(k: str) -> str:
+    """The inverse of ``_ldm_vae_key`` on the encoder side: diffusers key -> 'first_stage_model.' key (prefix not included)."""
+    if k.startswith("quant_conv."):
+        return k
+    p = k.split(".")[1:]
+    ren = {"conv_shortcut": "nin_shortcut"}
+    if p[0] in ("conv_in", "conv_out"):
+        return "encoder." + ".".join(p)
+    if p[0] == "conv_norm_out":
+        return "encoder.norm_out." + p[1]
+    if p[0] == "mid_block":
+        if p[1] == "resnets":
+            return f"encoder.mid.block_{int(p[2]) + 1}." + ".".join(ren.get(t, t) for t in p[3:])
+        rest = ".".join(p[3:-1])
+        a = {"group_norm": "norm", "to_q": "q", "to_k": "k", "to_v": "v", "to_out.0": "proj_out"}[rest]
+        return f"encoder.mid.attn_1.{a}." + p[-1]
+    if p[2] == "resnets":
+        return f"encoder.down.{p[1]}.block.{p[3]}." + ".".join(ren.get(t, t) for t in p[4:])
+    return f"encoder.down.{p[1]}.downsample.conv." + p[-1]
 
 
 def single_file_prediction_type(raw: dict, sd2: bool) -> str:
@@ -578,6 +682,7 @@ def load_single_file(path: str, with_meta: bool = False):
                 continue                                                      # CLIPTextModel has no projection
             for nk, tf in _openclip_text_key(kk):
                 csd[nk] = (v if tf is None else v.chunk(3, dim=0)[tf[1]]).to(torch.float16).contiguous()
+    vsd = split_vae_encoder(vsd)
     if "conv_in.weight" not in usd:
         raise RuntimeError(f"{path}: no model.diffusion_model.* tensors (not an original-layout SD checkpoint)")
     boc = (usd["conv_in.weight"].shape[0], usd["down_blocks.1.resnets.0.conv1.weight"].shape[0],
@@ -655,8 +760,8 @@ def load_single_file_sdxl(path: str):
                 usd[nk] = v.to(torch.float16)
         elif k.startswith("first_stage_model."):
             nk = _ldm_vae_key(k[len("first_stage_model."):])
-            if nk:
-                vsd[nk] = v.to(torch.float16)
+            if nk and not (nk.startswith("encoder.") or nk.startswith("quant_conv.")):      # no image-to-image for SDXL: the
+                vsd[nk] = v.to(torch.float16)                                               # encoder side is not kept
         elif k.startswith("conditioner.embedders.0.transformer."):
             kk = k[len("conditioner.embedders.0.transformer."):]
             kk = kk[len("text_model."):] if kk.startswith("text_model.") else kk
