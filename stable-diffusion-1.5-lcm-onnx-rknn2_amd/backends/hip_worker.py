@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from ..lib import LcmHipError
-from ..pipeline import LcmHipPipeline
+from ..pipeline import LcmHipPipeline, draw_noise, draw_noise_hires, draw_noise_img2img
 from ..prompt import HipPromptEncoder
 from ..scheduler import LCMSchedule
 from .. import weights as _weights
@@ -212,6 +212,27 @@ def decode_jpeg(data) -> np.ndarray:
     return pil()
 
 
+def _rows(x, idx, n):
+    """The per-request conditioning rows ``idx`` of a batch of n: tensors with n leading rows are gathered, tuples (SDXL's
+    ``added``) and dicts walked, anything else passed through; the whole batch in order is returned as it is."""
+    if list(idx) == list(range(n)):
+        return x
+    if isinstance(x, torch.Tensor) and x.dim() > 0 and x.shape[0] == n:
+        return x[idx]
+    if isinstance(x, tuple):
+        return tuple(_rows(y, idx, n) for y in x)
+    if isinstance(x, dict):
+        return {k: _rows(v, idx, n) for k, v in x.items()}
+    return x
+
+
+def _take(res, out, idx):
+    """The pipeline's result dict of the items ``idx`` -> their (rgb, pool8 row) slots of ``res``."""
+    for b, i in enumerate(idx):
+        res[i] = (out["rgb"][b], out["pool8"][b:b + 1])
+    return res
+
+
 class _Engine:
     """Everything resident for one (family, device, checkpoint): the pipeline (weights, launch plans, captured graphs), the
     text encoders, the style adapters and the micro-batching dispatcher.  The reference builds one pipeline -- and one
@@ -359,25 +380,29 @@ class _Engine:
                     pe, kw = self.family_cls._conditioning(self, reqs, width, height, g, lane)
                 t1 = _t.perf_counter()
                 noises = [it[2] for it in items] if all(len(it) > 2 and it[2] is not None for it in items) else None
-                if _controlnet.is_control_key(key):
-                    hints = np.stack([it[3] for it in items])
-                    out = pipe.generate(pe, [it[1] for it in items], width, height, steps, g, noises=noises, lane=lane,
-                                        control=(hints, key[7]), **kw)
-                    res = [(out["rgb"][i], out["pool8"][i:i + 1]) for i in range(len(items))]
-                    with self._stats_lock:
-                        self.stats["unet_evals"] += steps
-                        self.stats["controlnet_evals"] += steps
-                elif _hires.is_hires_key(key):
-                    res = self._run_hires(pipe, key, items, noises, pe, kw, lane, stream)
-                elif _img2img.is_img2img_key(key):
-                    res = self._run_img2img(pipe, key, items, noises, pe, kw, lane, stream)
-                elif len(key) > 6:
+                seeds = [it[1] for it in items]
+                if _hires.is_hires_key(key):         # key = plain key + (KEY_TAG, target width, target height, hr_steps, strength, mode)
+                    tw, th, hr_steps, strength, mode = key[7:12]
+                    cap = pipe.hires_batch_cap(tw, th, hr_steps, strength, g, lane=lane, sizes=self.batch_sizes)
+                    res = self._run_capped(items, noises, pe, kw, cap, stream, "hires_requests", lambda idx, sub_pe, sub_noises, sub_kw:
+                                           pipe.generate(sub_pe, [seeds[i] for i in idx], width, height, steps, g, noises=sub_noises,
+                                                         lane=lane, hires=(tw, th, hr_steps, strength, mode), **sub_kw))
+                elif _img2img.is_img2img_key(key):   # key = plain key + (KEY_TAG, strength); items carry the fitted picture
+                    cap = pipe.img2img_batch_cap(width, height, steps, key[7], g, lane=lane, sizes=self.batch_sizes)
+                    res = self._run_capped(items, noises, pe, kw, cap, stream, "img2img_requests", lambda idx, sub_pe, sub_noises, sub_kw:
+                                           pipe.generate_img2img(sub_pe, [seeds[i] for i in idx], np.stack([items[i][3] for i in idx]),
+                                                                 width, height, steps, key[7], g, noises=sub_noises, lane=lane, **sub_kw))
+                elif len(key) > 6 and not _controlnet.is_control_key(key):
                     res = self._run_refine(pipe, key, items, noises, pe, kw, lane, stream)
-                else:
-                    out = pipe.generate(pe, [it[1] for it in items], width, height, steps, g, noises=noises, lane=lane, **kw)
-                    res = [(out["rgb"][i], out["pool8"][i:i + 1]) for i in range(len(items))]
+                else:                                # plain, or ControlNet: the hints ride along, the scale is key[7]
+                    control = _controlnet.is_control_key(key)
+                    if control:
+                        kw = dict(kw, control=(np.stack([it[3] for it in items]), key[7]))
+                    out = pipe.generate(pe, seeds, width, height, steps, g, noises=noises, lane=lane, **kw)
+                    res = _take([None] * len(items), out, range(len(items)))
                     with self._stats_lock:
                         self.stats["unet_evals"] += steps
+                        self.stats["controlnet_evals"] += steps if control else 0
             finally:
                 self._leave_style()
         t2 = _t.perf_counter()
@@ -396,18 +421,9 @@ class _Engine:
         idents = [_refine.request_ident(it[0], key, it[1]) for it in items]
         found = [cache.deepest(idn, d, p) if cache.cap > 0 else (None, None) for idn in idents]
         res = [None] * len(items)
-
-        def rows(x, idx):                            # per-request conditioning rows of a sub-batch
-            if isinstance(x, torch.Tensor) and x.dim() > 0 and x.shape[0] == len(items):
-                return x[idx]
-            if isinstance(x, tuple):
-                return tuple(rows(y, idx) for y in x)
-            return x
         for k0, idx in _refine.group_by_start([f[0] for f in found], self.batch_sizes):
-            whole = len(idx) == len(items)
             with torch.cuda.stream(stream):          # the rows are gathered on the lane's stream, behind the text encoder
-                sub_pe = pe if whole else pe[idx]
-                sub_kw = kw if whole else {n: rows(v, idx) for n, v in kw.items()}
+                sub_pe, sub_kw = _rows((pe, kw), idx, len(items))
             start = None if k0 is None else (k0, [found[i][1] for i in idx])
             out = pipe.generate(sub_pe, [items[i][1] for i in idx], width, height, steps, g,
                                 noises=[noises[i] for i in idx] if noises is not None else None, lane=lane,
@@ -427,64 +443,30 @@ class _Engine:
                 self.stats["refine_cache_hits"] += len(idx) if k0 is not None else 0
                 self.stats["refine_cache_misses"] += len(idx) if k0 is None else 0
                 self.stats["refine_cache_puts"] += puts
-            for b, i in enumerate(idx):
-                res[i] = (out["rgb"][b], out["pool8"][b:b + 1])
+            _take(res, out, idx)
         return res
 
-    def _run_capped(self, items, noises, pe, kw, cap, stream, call):
-        """A batch as passes of at most ``cap`` items (the largest plan size whose split-K workspace need fits the lane: a
-        request never fails on workspace a smaller pass would have served; bit-neutral, a request's bytes do not depend on its
-        batch).  call(idx, sub_pe, sub_noises, sub_kw) -> the pipeline's result dict for the items ``idx``.
-        -> (per-item (rgb, pool8 row), UNet evaluations)."""
+    def _run_capped(self, items, noises, pe, kw, cap, stream, stat, call):
+        """A hires or image-to-image batch as passes of at most ``cap`` items (the largest plan size whose split-K workspace
+        need fits the lane -- the pipeline's hires_batch_cap / img2img_batch_cap: a request never fails on workspace a smaller
+        pass would have served; bit-neutral, a request's bytes do not depend on its batch).  call(idx, sub_pe, sub_noises,
+        sub_kw) -> the pipeline's result dict for the items ``idx``; stat: the requests counter of the kind.
+        -> per-item (rgb, pool8 row)."""
         n = len(items)
         res = [None] * n
-
-        def rows(x, idx):                            # per-request conditioning rows of a sub-batch
-            if isinstance(x, torch.Tensor) and x.dim() > 0 and x.shape[0] == n:
-                return x[idx]
-            return x
         evals = 0
         for i0 in range(0, n, min(cap, n)):
             idx = list(range(i0, min(n, i0 + cap)))
             if len(idx) not in self.batch_sizes:     # a tail that is no plan size: its last item repeated (results dropped)
                 idx += [idx[-1]] * (min(s for s in self.batch_sizes if s >= len(idx)) - len(idx))
-            whole = idx == list(range(n))
             with torch.cuda.stream(stream):          # the rows are gathered on the lane's stream, behind the text encoder
-                sub_pe = pe if whole else pe[idx]
-                sub_kw = kw if whole else {name: rows(v, idx) for name, v in kw.items()}
+                sub_pe, sub_kw = _rows((pe, kw), idx, n)
             out = call(idx, sub_pe, [noises[i] for i in idx] if noises is not None else None, sub_kw)
             evals += out["unet_evals"]
-            for b, i in enumerate(idx):
-                res[i] = (out["rgb"][b], out["pool8"][b:b + 1])
-        return res, evals
-
-    def _run_hires(self, pipe, key, items, noises, pe, kw, lane, stream):
-        """The passes of a hires batch (key = plain key + (KEY_TAG, target width, target height, hr_steps, strength, mode)).  The
-        second stage at a large target can need more split-K workspace than the lane has: the need is computed from the plan
-        and the batch runs as passes of the largest plan size that fits (_run_capped)."""
-        width, height, steps, g = key[:4]
-        tw, th, hr_steps, strength, mode = key[7:12]
-        cap = pipe.hires_batch_cap(tw, th, hr_steps, strength, g, lane=lane, sizes=self.batch_sizes)
-        res, evals = self._run_capped(items, noises, pe, kw, cap, stream, lambda idx, sub_pe, sub_noises, sub_kw: pipe.generate(
-            sub_pe, [items[i][1] for i in idx], width, height, steps, g, noises=sub_noises, lane=lane,
-            hires=(tw, th, hr_steps, strength, mode), **sub_kw))
+            _take(res, out, idx)
         with self._stats_lock:
             self.stats["unet_evals"] += evals
-            self.stats["hires_requests"] += len({id(it) for it in items})
-        return res
-
-    def _run_img2img(self, pipe, key, items, noises, pe, kw, lane, stream):
-        """The passes of an image-to-image batch (key = plain key + (KEY_TAG, strength); items carry the fitted picture), capped
-        like a hires batch -- by the workspace need of the strength-cut pass AND of the encoder stage (img2img_batch_cap)."""
-        width, height, steps, g = key[:4]
-        strength = key[7]
-        cap = pipe.img2img_batch_cap(width, height, steps, strength, g, lane=lane, sizes=self.batch_sizes)
-        res, evals = self._run_capped(items, noises, pe, kw, cap, stream, lambda idx, sub_pe, sub_noises, sub_kw: pipe.generate_img2img(
-            sub_pe, [items[i][1] for i in idx], np.stack([items[i][3] for i in idx]), width, height, steps, strength, g,
-            noises=sub_noises, lane=lane, **sub_kw))
-        with self._stats_lock:
-            self.stats["unet_evals"] += evals
-            self.stats["img2img_requests"] += len({id(it) for it in items})
+            self.stats[stat] += len({id(it) for it in items})
         return res
 
     def start_batcher(self):
@@ -780,47 +762,39 @@ class HipLcmWorker:
     def _run_batch(self, key, items):
         return self._engine.run_batch(key, items)
 
+    @staticmethod
+    def _drawable(key, *more) -> bool:
+        """Can the request's noise be drawn ahead?  Its sizes are positive multiples of 8 and it has a step; anything else is
+        left to the pipeline's own error."""
+        return all(v % 8 == 0 and v > 0 for v in key[:2] + more) and key[2] >= 1
+
     def _prepare(self, req, key):
-        """-> (req, seed, noise): the seed policy of cuda_worker.py:210-213 and the request's RNG stream."""
+        """-> (req, seed, noise[, hint | picture]): the seed policy of cuda_worker.py:210-213 and the request's RNG stream."""
         eng = self._engine
         seed = int(req.seed) if getattr(req, "seed", None) is not None else int(torch.randint(0, 100_000_000, (1,)).item())
         # the request's RNG stream (initial latents, then one draw per remaining step) is drawn HERE, on the caller's
         # thread: pool threads do it in parallel and the GPU dispatcher's serial path shrinks by ~0.5 ms per request
-        from ..pipeline import draw_noise
-        noise = None
-        n_draws = key[2]
-        if _controlnet.is_control_key(key):
-            eng.ensure_controlnet()                  # lazily, on the caller's thread; raises for this job
-            hint = _controlnet.fit_hint(_controlnet.parse_control(req)[1], key[0], key[1])
-            noise = None
-            if key[0] % 8 == 0 and key[1] % 8 == 0 and key[0] > 0 and key[1] > 0 and key[2] >= 1:
-                noise = draw_noise(seed, key[1] // 8, key[0] // 8, n_draws - 1, eng.pipe.sched.init_noise_sigma)
-            return (req, seed, noise, hint)
+        sched = eng.pipe.sched
+        h8, w8, steps = key[1] // 8, key[0] // 8, key[2]
+        n_draws, more = steps, ()
         if _img2img.is_img2img_key(key):             # encoder on first use, the schedule's own error, the picture, the draws
             eng.ensure_vae_encoder()
-            _img2img.check_schedule(eng.pipe.sched, key[2], key[7])
+            _refine.check_schedule(sched, steps, key[7])
             pic = _img2img.fit_init(_img2img.parse_img2img(req)[1], key[0], key[1])
-            if key[0] % 8 == 0 and key[1] % 8 == 0 and key[0] > 0 and key[1] > 0 and key[2] >= 1:
-                from ..pipeline import draw_noise_img2img
-                noise = draw_noise_img2img(seed, key[1] // 8, key[0] // 8, key[2])
-            return (req, seed, noise, pic)
+            return (req, seed, draw_noise_img2img(seed, h8, w8, steps) if self._drawable(key) else None, pic)
         if _hires.is_hires_key(key):                 # the schedule's own error first, then the draws at both shapes
             tw, th, hr_steps, strength = key[7:11]
-            _hires.check_schedule(eng.pipe.sched, hr_steps, strength)
-            if all(v % 8 == 0 and v > 0 for v in (key[0], key[1], tw, th)) and key[2] >= 1:
-                from ..pipeline import draw_noise_hires
-                noise = draw_noise_hires(seed, key[1] // 8, key[0] // 8, key[2], th // 8, tw // 8, hr_steps,
-                                         eng.pipe.sched.init_noise_sigma)
-            return (req, seed, noise)
-        if len(key) > 6:                             # refinement: the schedule's own error first, then the whole chain's draws
-            try:
-                eng.pipe.sched.timesteps(key[2], key[6])
-            except ValueError as e:
-                raise RuntimeError(str(e))
-            n_draws = _refine.noise_draws(key[2], key[7])
-        if key[0] % 8 == 0 and key[1] % 8 == 0 and key[0] > 0 and key[1] > 0 and key[2] >= 1:
-            noise = draw_noise(seed, key[1] // 8, key[0] // 8, n_draws - 1, eng.pipe.sched.init_noise_sigma)
-        return (req, seed, noise)
+            _refine.check_schedule(sched, hr_steps, strength)
+            return (req, seed, draw_noise_hires(seed, h8, w8, steps, th // 8, tw // 8, hr_steps, sched.init_noise_sigma)
+                    if self._drawable(key, tw, th) else None)
+        if _controlnet.is_control_key(key):
+            eng.ensure_controlnet()                  # lazily, on the caller's thread; raises for this job
+            more = (_controlnet.fit_hint(_controlnet.parse_control(req)[1], key[0], key[1]),)
+        elif len(key) > 6:                           # refinement: the schedule's own error first, then the whole chain's draws
+            _refine.check_schedule(sched, steps, key[6])
+            n_draws = _refine.noise_draws(steps, key[7])
+        noise = draw_noise(seed, h8, w8, n_draws - 1, sched.init_noise_sigma) if self._drawable(key) else None
+        return (req, seed, noise) + more
 
     def _submit(self, job):
         eng = self._engine

@@ -6,6 +6,7 @@ them).  No GPU code here: the chain itself is ``LcmHipPipeline.generate(..., hir
 from __future__ import annotations
 
 from ..lib import UPSCALE_MODES
+from .refine import check_schedule  # noqa: F401  (the one schedule check, under this module's name too)
 
 MIN_STRENGTH, MAX_STRENGTH = 0.05, 1.0
 MIN_SCALE, MAX_SCALE = 1.0, 4.0
@@ -70,13 +71,3 @@ def parse_hires(req, width: int, height: int, steps: int):
     if not isinstance(up, str) or up not in UPSCALE_MODES:
         raise RuntimeError(f"Invalid hr_upscaler {up!r}: the latent upscalers served are " + ", ".join(repr(k) for k in UPSCALE_MODES))
     return (tw, th, hr_steps, round(strength, 6), UPSCALE_MODES[up])
-
-
-def check_schedule(sched, hr_steps: int, strength: float):
-    """diffusers' own error for hr_steps > int(original_inference_steps x strength), as a RuntimeError of the job (refinement
-    raises the same text)."""
-    try:
-        sched.timesteps(int(hr_steps), float(strength))
-    except ValueError as e:
-        raise RuntimeError(str(e))
-

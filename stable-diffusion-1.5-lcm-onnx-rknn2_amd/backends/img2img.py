@@ -11,6 +11,8 @@ import binascii
 import numpy as np
 
 from . import controlnet as _controlnet
+from .hires import _number
+from .refine import check_schedule  # noqa: F401  (the one schedule check, under this module's name too)
 
 MIN_STRENGTH, MAX_STRENGTH = 0.05, 1.0
 DEFAULT_STRENGTH = 0.75                                    # A1111's img2img default
@@ -67,15 +69,7 @@ def parse_img2img(req):
     memo = getattr(req, _MEMO, None)
     if memo is not None and memo[0] is src:                # keyed on the object as sent: a base64 entry is decoded once too
         return memo[1]
-    v = getattr(req, "denoising_strength", None)
-    try:
-        if isinstance(v, bool):
-            raise ValueError
-        s = DEFAULT_STRENGTH if v is None else float(v)
-    except (TypeError, ValueError):
-        raise RuntimeError(f"Invalid denoising_strength {v!r}, expected a number in [{MIN_STRENGTH}, {MAX_STRENGTH}]")
-    if not MIN_STRENGTH <= s <= MAX_STRENGTH:             # NaN fails both comparisons
-        raise RuntimeError(f"Invalid denoising_strength {v!r}, expected a number in [{MIN_STRENGTH}, {MAX_STRENGTH}]")
+    s = _number(req, "denoising_strength", MIN_STRENGTH, MAX_STRENGTH, DEFAULT_STRENGTH)
     out = (round(s, 6), decode_init(_unbase64(src) if b64 else src))
     try:
         object.__setattr__(req, _MEMO, (src, out))
@@ -87,12 +81,3 @@ def parse_img2img(req):
 def fit_init(img: np.ndarray, width: int, height: int) -> np.ndarray:
     """The picture at the request's size: as is when it fits, else PIL LANCZOS in RGB (backends/controlnet.fit_hint)."""
     return _controlnet.fit_hint(img, width, height)
-
-
-def check_schedule(sched, steps: int, strength: float):
-    """diffusers' own error for steps > int(original_inference_steps x strength), as a RuntimeError of the job (refinement and
-    hires raise the same text)."""
-    try:
-        sched.timesteps(int(steps), float(strength))
-    except ValueError as e:
-        raise RuntimeError(str(e))

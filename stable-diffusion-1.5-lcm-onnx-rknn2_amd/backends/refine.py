@@ -58,6 +58,15 @@ def noise_draws(steps: int, passes: int) -> int:
     return int(steps) * (int(passes) + 1)
 
 
+def check_schedule(sched, steps: int, strength: float):
+    """diffusers' own error for steps > int(original_inference_steps x strength), as a RuntimeError of the job: the one check
+    of refinement, hires (its hr_steps) and image-to-image requests."""
+    try:
+        sched.timesteps(int(steps), float(strength))
+    except ValueError as e:
+        raise RuntimeError(str(e))
+
+
 def cache_bytes_from_env() -> int:
     try:
         mb = float(os.environ.get("LCM_REFINE_CACHE_MB", "64") or 0)

@@ -56,22 +56,23 @@ def check_size(width: int, height: int) -> None:
         raise LcmHipError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
 
 
-def draw_noise(seed: int, h: int, w: int, n_extra: int, sigma: float = 1.0):
+def _draw(seed: int, *groups):
+    """A request's RNG stream: one CPU generator seeded with ``seed``; per (h, w, count) group, in order, ``count`` fp32
+    [1,4,h,w] tensors -> one list per group."""
     g = torch.Generator(device="cpu").manual_seed(int(seed))
-    shape = (1, 4, h, w)
-    lat = torch.randn(shape, generator=g, dtype=torch.float32) * sigma
-    extra = [torch.randn(shape, generator=g, dtype=torch.float32) for _ in range(n_extra)]
-    return lat, extra
+    return [[torch.randn((1, 4, h, w), generator=g, dtype=torch.float32) for _ in range(int(n))] for h, w, n in groups]
+
+
+def draw_noise(seed: int, h: int, w: int, n_extra: int, sigma: float = 1.0):
+    (lat,), extra = _draw(seed, (h, w, 1), (h, w, n_extra))
+    return lat * sigma, extra
 
 
 def draw_noise_hires(seed: int, h: int, w: int, steps: int, h2: int, w2: int, hr_steps: int, sigma: float = 1.0):
     """A hires request's RNG stream (module docstring) -> (latents, the steps - 1 step noises at [1,4,h,w], the re-noise tensor
     followed by the hr_steps - 1 step noises at [1,4,h2,w2])."""
-    g = torch.Generator(device="cpu").manual_seed(int(seed))
-    lat = torch.randn((1, 4, h, w), generator=g, dtype=torch.float32) * sigma
-    lo = [torch.randn((1, 4, h, w), generator=g, dtype=torch.float32) for _ in range(int(steps) - 1)]
-    hi = [torch.randn((1, 4, h2, w2), generator=g, dtype=torch.float32) for _ in range(int(hr_steps))]
-    return lat, lo, hi
+    (lat,), lo, hi = _draw(seed, (h, w, 1), (h, w, int(steps) - 1), (h2, w2, hr_steps))
+    return lat * sigma, lo, hi
 
 
 def draw_noise_img2img(seed: int, h: int, w: int, steps: int, sigma: float = 1.0):
@@ -79,9 +80,7 @@ def draw_noise_img2img(seed: int, h: int, w: int, steps: int, sigma: float = 1.0
     draw; e1, the re-noise draw at the first timestep of the strength-cut schedule; then the steps - 1 step noises
     -> (e0, [e1, e2, ...]) (``steps`` tensors in the list), each fp32 [1,4,h,w].  ``sigma`` is accepted for symmetry with
     ``draw_noise`` and unused: neither draw is an initial latent, so nothing is multiplied by init_noise_sigma."""
-    g = torch.Generator(device="cpu").manual_seed(int(seed))
-    e0 = torch.randn((1, 4, h, w), generator=g, dtype=torch.float32)
-    rest = [torch.randn((1, 4, h, w), generator=g, dtype=torch.float32) for _ in range(int(steps))]
+    (e0,), rest = _draw(seed, (h, w, 1), (h, w, steps))
     return e0, rest
 
 
@@ -228,18 +227,13 @@ class LcmHipPipeline:
         # (above); launches on streams that are no lane's (tests, tools) use a device-wide default that no lane shares.
         self._splitk_ws = self.lanes[0].splitk_ws
         ops.set_workspace(_default_workspace(self.device))
-        if "LCM_CONV_IMPL" in os.environ:            # A/B switches for kernel work
-            ops.set_conv_impl(int(os.environ["LCM_CONV_IMPL"]))
-        if "LCM_GN_FUSED_BYTES" in os.environ:
-            ops.set_gn_fused_bytes(int(os.environ["LCM_GN_FUSED_BYTES"]))
-        if "LCM_PERSIST_N" in os.environ:
-            ops.set_persist_n(int(os.environ["LCM_PERSIST_N"]))
-        if "LCM_HALO_PIPE" in os.environ:
-            ops.set_halo_pipe_threshold(int(os.environ["LCM_HALO_PIPE"]))
-        if "LCM_ATTN_KSPLIT" in os.environ:          # 0: unsplit streaming attention at every length (changes the bits of the >= 1024-key levels)
-            ops.set_attention_ksplit(int(os.environ["LCM_ATTN_KSPLIT"]))
-        if "LCM_KERNEL_VARIANT" in os.environ:
-            ops.set_kernel_variant(int(os.environ["LCM_KERNEL_VARIANT"]))
+        # A/B switches for kernel work.  LCM_ATTN_KSPLIT=0: unsplit streaming attention at every length (changes the bits of the
+        # >= 1024-key levels)
+        for env, setter in (("LCM_CONV_IMPL", ops.set_conv_impl), ("LCM_GN_FUSED_BYTES", ops.set_gn_fused_bytes),
+                            ("LCM_PERSIST_N", ops.set_persist_n), ("LCM_HALO_PIPE", ops.set_halo_pipe_threshold),
+                            ("LCM_ATTN_KSPLIT", ops.set_attention_ksplit), ("LCM_KERNEL_VARIANT", ops.set_kernel_variant)):
+            if env in os.environ:
+                setter(int(os.environ[env]))
 
     # ------------------------------------------------------------------------------------------
     def lane(self, index: int) -> _Lane:
@@ -254,10 +248,7 @@ class LcmHipPipeline:
         the UNet (weights.check_controlnet_matches raises otherwise).  Plans with a hint are dropped: they bake its pointers in."""
         with self._build_lock:
             for L in self.lanes:
-                for key in [k for k, P in L.plans.items() if P.control is not None]:
-                    P = L.plans.pop(key)
-                    if P.graph is not None:
-                        P.graph.close()
+                self._close_graphs(L, lambda P: P.control is not None)
                 L.controlnet = L._controlnet_of = None
             self.controlnet = None if sd is None else ControlNetHip(sd, cfg, self.unet.cfg, self.device)
         return self.controlnet
@@ -329,9 +320,9 @@ class LcmHipPipeline:
                          negative_embeds=None, want_float=False, noises=None, lane=0):
         """Image-to-image with the semantics of diffusers' LatentConsistencyModelImg2ImgPipeline: images_u8 uint8 [B,H,W,3] at the
         request's size -> AutoencoderKL encoder -> z = (mean + exp(0.5 clamp(logvar, -30, 20)) e0) scaling_factor -> re-noised to
-        the first timestep of ``timesteps(steps, strength)`` with e1 -> ``steps`` LCM steps over that schedule -> decode.  On the
-        lane's stream, nothing copied to the host in between: the encoder stage (its own captured graph; eager with want_float or
-        use_graph=False), lcm_vae_posterior_renoise into the state of the "from-state" plan, that plan.  noises: optional
+        the first timestep of ``timesteps(steps, strength)`` with e1 -> ``steps`` LCM steps over that schedule -> decode.  The
+        front stage of the request (``_request``) is the encoder stage (its own captured graph; eager with want_float or
+        use_graph=False) and lcm_vae_posterior_renoise into the state of the "from-state" plan.  noises: optional
         per-request ``draw_noise_img2img`` results.  Returns the usual dict plus ``init_latents`` (host fp32 [B,4,h,w]: z) and
         ``unet_evals`` = steps (doubled under classifier-free guidance); with want_float also ``image`` and ``moments`` (host fp32
         [B,8,h,w]: the posterior's mean | logvar)."""
@@ -347,54 +338,38 @@ class LcmHipPipeline:
         img = torch.as_tensor(images_u8)
         if img.dtype != torch.uint8 or tuple(img.shape) != (B, height, width, 3):
             raise LcmHipError(f"init images must be uint8 [B={B}, H={height}, W={width}, 3], got {img.dtype} {tuple(img.shape)}")
-        do_cfg = (guidance_scale > 1.0) and not self.unet.has_cond
-        if do_cfg and negative_embeds is None:
-            raise LcmHipError("classifier-free guidance needs negative_embeds")
+        do_cfg = self._do_cfg(guidance_scale, negative_embeds)
         ts = self.sched.timesteps(steps, strength)       # diffusers' error for steps > original_steps x strength, before any plan
         nsa, nsb = self.sched.renoise_coefficients(ts[0])
         h, w = height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR
-        P = self.plan(B, h, w, steps, do_cfg, guidance_scale, lane=lane, refine=(strength, 1, True), kind="from-state")
+        P = self._from_state_plan(B, width, height, steps, strength, guidance_scale, lane)
         L = P.lane
         self.lane_vae_encoder(L)                         # raises for a checkpoint without an encoder, before anything is queued
         E = self._enc_plan(L, B, height, width)
-        stream = L.stream
-        with torch.cuda.stream(stream):
-            for b, s in enumerate(seeds):
-                e0, rest = noises[b] if noises is not None else draw_noise_img2img(s, h, w, steps)
-                if len(rest) != steps:
-                    raise LcmHipError(f"request {b}: 1 + {len(rest)} noise tensors drawn ahead, the chain needs 1 + {steps}")
-                E.h_e0[b].copy_(e0[0])
-                for i, n in enumerate(rest):
-                    P.h_noise[i, b].copy_(n[0])
-            E.h_img.copy_(img)
-            eager = (not self.use_graph) or want_float
-            if not eager:                            # the sampler's graph first: its warm-up pass overwrites the plan's state
-                self._ensure_graph(P, guidance_scale)
+        for b, s in enumerate(seeds):
+            e0, rest = noises[b] if noises is not None else draw_noise_img2img(s, h, w, steps)
+            if len(rest) != steps:
+                raise LcmHipError(f"request {b}: 1 + {len(rest)} noise tensors drawn ahead, the chain needs 1 + {steps}")
+            E.h_e0[b].copy_(e0[0])
+            for i, n in enumerate(rest):
+                P.h_noise[i, b].copy_(n[0])
+        E.h_img.copy_(img)
+
+        def upload():
             E.img.copy_(E.h_img, non_blocking=True)
             E.e0.copy_(E.h_e0, non_blocking=True)
-            P.noise.copy_(P.h_noise, non_blocking=True)
-            self._upload_text(P, pe, negative_embeds, guidance_scale)
-            # ---- encoder -> hand-over -> the strength-cut pass, in stream order ----
+
+        def front(eager):                                # encoder -> hand-over into the strength-cut pass's state
             pre_m, pre_l = self._encode_stage(L, E, eager)
             enc = L.vae_enc
             ops.vae_posterior_renoise(pre_m, pre_l, enc.w["quant.w"], enc.w["quant.b"], E.e0, P.noise[0],
                                       self.vae.cfg["scaling_factor"], nsa, nsb, P.xk[0], P.lat, B, h, w,
                                       moments=E.moments if want_float else None, dup=do_cfg)
-            if eager:
-                with self._build_lock:
-                    self._enqueue(P, guidance_scale, want_float=want_float)
-            else:
-                P.graph.launch()
-            final = P.lat[B:] if do_cfg else P.lat
-            P.h_rgb.copy_(P.rgb, non_blocking=True)
-            P.h_pool8.copy_(P.pool8, non_blocking=True)
-            P.h_latout.copy_(final, non_blocking=True)
-            E.h_z.copy_(P.xk[0], non_blocking=True)
-            stream.synchronize()
-        out = dict(rgb=P.h_rgb.numpy().copy(), latents=P.h_latout.numpy().copy(), pool8=P.h_pool8.numpy().copy(),
-                   init_latents=E.h_z.numpy().copy(), unet_evals=steps * (2 if do_cfg else 1))
+
+        out, _ = self._request([P], pe, negative_embeds, guidance_scale, upload, front, want_float=want_float,
+                               more=lambda: E.h_z.copy_(P.xk[0], non_blocking=True))
+        out.update(init_latents=E.h_z.numpy().copy(), unet_evals=steps * (2 if do_cfg else 1))
         if want_float:
-            out["image"] = P.img_f32.cpu().numpy()
             out["moments"] = E.moments.cpu().numpy()
         return out
 
@@ -530,16 +505,19 @@ class LcmHipPipeline:
             stream.synchronize()
         P.tuned = True
 
+    @staticmethod
+    def _close_graphs(L: _Lane, only=None):
+        """Close and forget the captured graphs of a lane with their plans: sampler plans and encoder stages, or -- with
+        only(P) -- just the sampler plans it picks."""
+        for plans in (L.plans,) if only is not None else (L.plans, L.enc_plans):
+            for key in [k for k, P in plans.items() if only is None or only(P)]:
+                g = plans.pop(key).graph
+                if g is not None:
+                    g.close()
+
     def drop_plans(self):
         for L in self.lanes:
-            for P in L.plans.values():
-                if P.graph is not None:
-                    P.graph.close()
-            L.plans.clear()
-            for E in L.enc_plans.values():
-                if E.graph is not None:
-                    E.graph.close()
-            L.enc_plans.clear()
+            self._close_graphs(L)
 
     def close(self):
         """Drop the captured graphs and take this pipeline's workspaces out of the library's per-stream table (the library
@@ -547,14 +525,7 @@ class LcmHipPipeline:
         lanes, self.lanes = getattr(self, "lanes", []), []
         self.controlnet = None
         for L in lanes:
-            for P in L.plans.values():
-                if P.graph is not None:
-                    P.graph.close()
-            L.plans.clear()
-            for E in getattr(L, "enc_plans", {}).values():
-                if E.graph is not None:
-                    E.graph.close()
-            getattr(L, "enc_plans", {}).clear()
+            self._close_graphs(L)
             try:
                 torch.cuda.synchronize(self.device)
                 ops.set_stream_workspace(L.stream, L.splitk_ws, forget=True)      # only if the entry is still this lane's
@@ -586,6 +557,24 @@ class LcmHipPipeline:
             P.wemb.copy_(torch.from_numpy(guidance_scale_embedding(gs, P.wemb.shape[1])).to(torch.float16),
                          non_blocking=True)
 
+    def _upload_added(self, P: _Plan, added, negative_added):
+        """SDXL: [pooled text embeds | sinusoid(time ids)] rows into the plan's buffer (the negative ones in front under
+        classifier-free guidance; zero pooled embeds when none are given), on the current stream."""
+        B, dim = P.B, self.unet.cfg["addition_time_embed_dim"]
+
+        def _add_rows(a):
+            pooled, tids = a
+            pooled = torch.as_tensor(pooled).to(torch.float32).reshape(B, -1).cpu()
+            sin = sinusoid_host(np.asarray(tids, dtype=np.float32).reshape(-1), dim)
+            return torch.cat([pooled, torch.from_numpy(sin).reshape(B, -1)], dim=1).to(torch.float16)
+        rows = _add_rows(added)
+        if P.do_cfg:
+            neg_rows = _add_rows(negative_added if negative_added is not None else (torch.zeros(B, rows.shape[1] - 6 * dim), added[1]))
+            P.add_in[:B].copy_(neg_rows, non_blocking=True)
+            P.add_in[B:].copy_(rows, non_blocking=True)
+        else:
+            P.add_in.copy_(rows, non_blocking=True)
+
     def _ensure_graph(self, P: _Plan, guidance_scale):
         """Tune, warm up (allocates every scratch buffer) and capture the plan's graph on its lane's stream, once."""
         if P.graph is None:
@@ -599,6 +588,31 @@ class LcmHipPipeline:
                         self._enqueue(P, guidance_scale)
                     P.graph = g
 
+    def _do_cfg(self, guidance_scale, negative_embeds=False) -> bool:
+        """Does guidance_scale mean classifier-free guidance here (guidance above 1 on a UNet without a guidance embedding)?  A
+        request passes its negative_embeds: None is then an error."""
+        do_cfg = (guidance_scale > 1.0) and not self.unet.has_cond
+        if do_cfg and negative_embeds is None:
+            raise LcmHipError("classifier-free guidance needs negative_embeds")
+        return do_cfg
+
+    def _from_state_plan(self, B, width, height, steps, strength, guidance_scale, lane) -> _Plan:
+        """The plan of one strength-cut pass that starts from a state the hand-over launch of a front stage wrote (hires
+        stage 2, image-to-image)."""
+        return self.plan(B, height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR, int(steps), self._do_cfg(guidance_scale),
+                         guidance_scale, lane=lane, refine=(float(strength), 1, True), kind="from-state")
+
+    def _recorded_need(self, holder, L: _Lane, run) -> int:
+        """_need_of one eager run() recorded on the lane's stream; remembered on ``holder`` (a plan)."""
+        need = getattr(holder, "_splitk_need", None)
+        if need is None:
+            with self._build_lock, torch.cuda.stream(L.stream):
+                with ops.recording() as recs:
+                    run()
+                L.stream.synchronize()
+            need = holder._splitk_need = self._need_of(recs)
+        return need
+
     def splitk_need(self, P: _Plan) -> int:
         """An upper bound of the split-K workspace bytes a pass of P's size needs PER IMAGE ROW of the UNet batch, from the plan's
         own launches: the K partition of a layer is a property of its per-image shape (include/lcm_hip.h, Determinism), so a
@@ -607,14 +621,7 @@ class LcmHipPipeline:
         library's error."""
         if P.B != 1:
             raise LcmHipError("splitk_need: a batch-1 plan, please")
-        need = getattr(P, "_splitk_need", None)
-        if need is None:
-            with self._build_lock, torch.cuda.stream(P.lane.stream):
-                with ops.recording() as recs:
-                    self._enqueue(P, 1.0)
-                P.lane.stream.synchronize()
-            need = P._splitk_need = self._need_of(recs)
-        return need
+        return self._recorded_need(P, P.lane, lambda: self._enqueue(P, 1.0))
 
     @staticmethod
     def _need_of(recs) -> int:
@@ -637,47 +644,83 @@ class LcmHipPipeline:
         times this."""
         L = self.lane(lane)
         E = self._enc_plan(L, 1, height, width)
-        need = getattr(E, "_splitk_need", None)
-        if need is None:
-            enc = self.lane_vae_encoder(L)
-            with self._build_lock, torch.cuda.stream(L.stream):
-                with ops.recording() as recs:
-                    enc.encode(E.img, 1, height, width)
-                L.stream.synchronize()
-            need = E._splitk_need = self._need_of(recs)
-        return need
+        enc = self.lane_vae_encoder(L)
+        return self._recorded_need(E, L, lambda: enc.encode(E.img, 1, height, width))
+
+    def _batch_cap(self, width, height, steps, strength, guidance_scale, lane, sizes, other_need=0) -> int:
+        """The largest pass size of ``sizes`` at which the from-state pass at width x height -- and a stage of ``other_need``
+        bytes per request before it on the same stream -- fits the lane's split-K workspace (at least the smallest: a batch-1
+        pass that does not fit raises the library's loud error when it runs)."""
+        P = self._from_state_plan(1, width, height, steps, strength, guidance_scale, lane)
+        per_request = max(self.splitk_need(P) * (2 if P.do_cfg else 1), other_need)   # classifier-free guidance: two UNet rows
+        fit = [n for n in sorted(sizes) if n * per_request <= P.lane.splitk_ws.numel() * 4]
+        return fit[-1] if fit else min(sizes)
 
     def img2img_batch_cap(self, width, height, steps, strength, guidance_scale=1.0, lane=0, sizes=(1, 2, 4, 8)) -> int:
         """The largest pass size of ``sizes`` at which BOTH stages of an image-to-image request at width x height fit the lane's
         split-K workspace: the strength-cut pass (hires_batch_cap's count, doubled rows under classifier-free guidance) and the
         encoder stage.  The stages run one after the other on one stream, so the need is the larger of the two."""
-        do_cfg = (guidance_scale > 1.0) and not self.unet.has_cond
-        P = self.plan(1, height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR, int(steps), do_cfg, guidance_scale, lane=lane,
-                      refine=(float(strength), 1, True), kind="from-state")
-        per_request = max(self.splitk_need(P) * (2 if do_cfg else 1), self.encoder_splitk_need(width, height, lane))
-        have = P.lane.splitk_ws.numel() * 4
-        fit = [n for n in sorted(sizes) if n * per_request <= have]
-        return fit[-1] if fit else min(sizes)
+        return self._batch_cap(width, height, steps, strength, guidance_scale, lane, sizes,
+                               self.encoder_splitk_need(width, height, lane))
 
     def hires_batch_cap(self, width, height, hr_steps, strength, guidance_scale=1.0, lane=0, sizes=(1, 2, 4, 8)) -> int:
         """The largest pass size of ``sizes`` whose second stage at width x height fits the lane's split-K workspace (at least
         the smallest: a batch-1 pass that does not fit raises the library's loud error when it runs)."""
-        do_cfg = (guidance_scale > 1.0) and not self.unet.has_cond
-        P = self.plan(1, height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR, int(hr_steps), do_cfg, guidance_scale, lane=lane,
-                      refine=(float(strength), 1, True), kind="from-state")
-        per_request = self.splitk_need(P) * (2 if do_cfg else 1)      # classifier-free guidance: two UNet rows per request
-        have = P.lane.splitk_ws.numel() * 4
-        fit = [n for n in sorted(sizes) if n * per_request <= have]
-        return fit[-1] if fit else min(sizes)
+        return self._batch_cap(width, height, hr_steps, strength, guidance_scale, lane, sizes)
+
+    def _run_plan(self, P: _Plan, guidance_scale, eager, want_float=False, taps=None):
+        """Run the plan now, on the current stream: plain launches under the build lock (they allocate scratch), or its graph."""
+        if eager:
+            with self._build_lock:
+                self._enqueue(P, guidance_scale, want_float=want_float, taps=taps)
+        else:
+            P.graph.launch()
+
+    def _request(self, plans, pe, negative_embeds, guidance_scale, upload=None, front=None, want_float=False, taps=None, more=None):
+        """The one sequence of every request kind, on the lane's stream.  plans: every plan of the request, the last one gives
+        the picture; their pinned staging (h_lat, h_noise) is filled.  upload(): the kind's own uploads (hint, picture, start
+        latents, SDXL rows); front(eager): the stage ahead of the last plan and its hand-over launch; more(): device-side
+        copies to queue after the read-backs -> (base result dict, what more() returned).  The rules:
+          * noise is drawn on the host, by the caller, before anything is launched: the graphs are RNG-free;
+          * the graphs of EVERY plan of the request are ensured before its uploads: a warm-up pass overwrites plan state;
+          * eager launches (use_graph=False, want_float, taps) hold _build_lock: they allocate scratch;
+          * everything runs on the lane's stream and nothing is copied to the host between the stages;
+          * exactly one synchronize per call, after the read-backs."""
+        P = plans[-1]
+        eager = (not self.use_graph) or want_float or taps is not None
+        stream = P.lane.stream
+        with torch.cuda.stream(stream):
+            if not eager:
+                for Q in plans:
+                    self._ensure_graph(Q, guidance_scale)
+            for Q in plans:
+                if Q.kind != "from-state":               # a from-state plan's first state comes from the hand-over launch
+                    Q.lat0.copy_(Q.h_lat, non_blocking=True)
+                Q.noise.copy_(Q.h_noise, non_blocking=True)
+                self._upload_text(Q, pe, negative_embeds, guidance_scale)
+            if upload is not None:
+                upload()
+            if front is not None:
+                front(eager)
+            self._run_plan(P, guidance_scale, eager, want_float, taps)
+            P.h_rgb.copy_(P.rgb, non_blocking=True)
+            P.h_pool8.copy_(P.pool8, non_blocking=True)
+            P.h_latout.copy_(P.lat[P.B:] if P.do_cfg else P.lat, non_blocking=True)
+            extra = more() if more is not None else None
+            stream.synchronize()
+        out = dict(rgb=P.h_rgb.numpy().copy(), latents=P.h_latout.numpy().copy(), pool8=P.h_pool8.numpy().copy())
+        if want_float:
+            out["image"] = P.img_f32.cpu().numpy()       # NHWC float, pre-clamp
+        return out, extra
 
     @torch.inference_mode()
     def generate_hires(self, prompt_embeds, seeds, width, height, steps, hires, guidance_scale=1.0, negative_embeds=None,
                        want_float=False, noises=None, lane=0):
         """Hires fix: sample at (width, height) for ``steps`` steps, upscale the denoised latents to (W2, H2) with latent upscaler
         ``mode`` (lib.UPSCALE_MODES), re-noise them to the first timestep of ``timesteps(hr_steps, strength)``, run ``hr_steps``
-        steps there and decode once.  hires = (W2, H2, hr_steps, strength, mode).  Three launches on the lane's stream with
-        nothing copied to the host in between: the "latents" plan at the base size (no VAE decode), lcm_latents_upscale_renoise
-        into the state of the "from-state" refinement plan at the target size, that plan.  noises: optional per-request
+        steps there and decode once.  hires = (W2, H2, hr_steps, strength, mode).  The front stage of the request (``_request``)
+        is the "latents" plan at the base size (no VAE decode) and lcm_latents_upscale_renoise into the state of the
+        "from-state" refinement plan at the target size.  noises: optional per-request
         ``draw_noise_hires`` results.  Returns the usual dict at the target size plus ``lowres_latents`` (host fp32 [B,4,h,w],
         the plain request's final latents bit for bit) and ``unet_evals`` = steps + hr_steps (doubled under classifier-free
         guidance); with want_float (eager launches) also ``image`` and ``upscaled_latents`` (host fp32 [B,4,H2/8,W2/8])."""
@@ -694,66 +737,39 @@ class LcmHipPipeline:
             raise LcmHipError(f"unknown latent upscaler mode {mode}: expected 0 (bilinear), 1 (bicubic) or 2 (nearest-exact)")
         if not (width <= W2 <= 4 * width and height <= H2 <= 4 * height):
             raise LcmHipError(f"hires target {W2}x{H2} outside [1, 4] x the base size {width}x{height}")
-        do_cfg = (guidance_scale > 1.0) and not self.unet.has_cond
-        if do_cfg and negative_embeds is None:
-            raise LcmHipError("classifier-free guidance needs negative_embeds")
+        do_cfg = self._do_cfg(guidance_scale, negative_embeds)
         self.sched.timesteps(steps)
         ts2 = self.sched.timesteps(hr_steps, strength)   # diffusers' error for hr_steps > original_steps x strength, before any plan
         nsa, nsb = self.sched.renoise_coefficients(ts2[0])
         h, w, h2, w2 = height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR, H2 // VAE_SCALE_FACTOR, W2 // VAE_SCALE_FACTOR
         P1 = self.plan(B, h, w, steps, do_cfg, guidance_scale, lane=lane, kind="latents")
-        P2 = self.plan(B, h2, w2, hr_steps, do_cfg, guidance_scale, lane=lane, refine=(strength, 1, True), kind="from-state")
-        stream = P1.lane.stream
-        with torch.cuda.stream(stream):
-            for b, s in enumerate(seeds):
-                l0, lo, hi = noises[b] if noises is not None else draw_noise_hires(s, h, w, steps, h2, w2, hr_steps,
-                                                                                   self.sched.init_noise_sigma)
-                if len(lo) != steps - 1 or len(hi) != hr_steps:
-                    raise LcmHipError(f"request {b}: {len(lo)} + {len(hi)} noise tensors drawn ahead, the chain needs "
-                                      f"{steps - 1} + {hr_steps}")
-                P1.h_lat[b].copy_(l0[0])
-                for i, n in enumerate(lo):
-                    P1.h_noise[i, b].copy_(n[0])
-                for i, n in enumerate(hi):
-                    P2.h_noise[i, b].copy_(n[0])
-            eager = (not self.use_graph) or want_float
-            if not eager:                            # both graphs first: a warm-up pass overwrites its plan's state
-                self._ensure_graph(P1, guidance_scale)
-                self._ensure_graph(P2, guidance_scale)
-            P1.lat0.copy_(P1.h_lat, non_blocking=True)
-            P1.noise.copy_(P1.h_noise, non_blocking=True)
-            P2.noise.copy_(P2.h_noise, non_blocking=True)
-            self._upload_text(P1, pe, negative_embeds, guidance_scale)
-            self._upload_text(P2, pe, negative_embeds, guidance_scale)
-            # ---- stage 1 -> hand-over -> stage 2, in stream order ----
-            if eager:
-                with self._build_lock:
-                    self._enqueue(P1, guidance_scale)
-            else:
-                P1.graph.launch()
-            low = P1.lat[B:] if do_cfg else P1.lat
+        P2 = self._from_state_plan(B, W2, H2, hr_steps, strength, guidance_scale, lane)
+        for b, s in enumerate(seeds):
+            l0, lo, hi = noises[b] if noises is not None else draw_noise_hires(s, h, w, steps, h2, w2, hr_steps,
+                                                                               self.sched.init_noise_sigma)
+            if len(lo) != steps - 1 or len(hi) != hr_steps:
+                raise LcmHipError(f"request {b}: {len(lo)} + {len(hi)} noise tensors drawn ahead, the chain needs "
+                                  f"{steps - 1} + {hr_steps}")
+            P1.h_lat[b].copy_(l0[0])
+            for i, n in enumerate(lo):
+                P1.h_noise[i, b].copy_(n[0])
+            for i, n in enumerate(hi):
+                P2.h_noise[i, b].copy_(n[0])
+        low = P1.lat[B:] if do_cfg else P1.lat
+
+        def front(eager):                                # stage 1 -> hand-over into stage 2's state
+            self._run_plan(P1, guidance_scale, eager)
             ops.latents_upscale_renoise(low, h, w, P2.noise[0], nsa, nsb, mode, P2.lat, B, h2, w2, x_up=P2.xk[0], dup=do_cfg)
-            if eager:
-                with self._build_lock:
-                    self._enqueue(P2, guidance_scale, want_float=want_float)
-            else:
-                P2.graph.launch()
-            final = P2.lat[B:] if do_cfg else P2.lat
-            P2.h_rgb.copy_(P2.rgb, non_blocking=True)
-            P2.h_pool8.copy_(P2.pool8, non_blocking=True)
-            P2.h_latout.copy_(final, non_blocking=True)
-            P1.h_latout.copy_(low, non_blocking=True)
-            stream.synchronize()
-        out = dict(rgb=P2.h_rgb.numpy().copy(), latents=P2.h_latout.numpy().copy(), pool8=P2.h_pool8.numpy().copy(),
-                   lowres_latents=P1.h_latout.numpy().copy(), unet_evals=(steps + hr_steps) * (2 if do_cfg else 1))
+
+        out, _ = self._request([P1, P2], pe, negative_embeds, guidance_scale, front=front, want_float=want_float,
+                               more=lambda: P1.h_latout.copy_(low, non_blocking=True))
+        out.update(lowres_latents=P1.h_latout.numpy().copy(), unet_evals=(steps + hr_steps) * (2 if do_cfg else 1))
         if want_float:
-            out["image"] = P2.img_f32.cpu().numpy()
             out["upscaled_latents"] = P2.xk[0].cpu().numpy()
         return out
 
     @torch.inference_mode()
-    def generate(
-self, prompt_embeds, seeds, width, height, steps, guidance_scale=1.0, negative_embeds=None,
+    def generate(self, prompt_embeds, seeds, width, height, steps, guidance_scale=1.0, negative_embeds=None,
                  want_float=False, taps=None, latents=None, added=None, negative_added=None, noises=None, lane=0,
                  strength=None, passes=0, start=None, control=None, hires=None):
         """prompt_embeds: [B,77,ctx] (any float dtype, host or device); seeds: B ints.  noises: optional per-request
@@ -791,10 +807,7 @@ self, prompt_embeds, seeds, width, height, steps, guidance_scale=1.0, negative_e
         check_size(width, height)
         h, w = height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR
         steps = int(steps)
-        has_cond = self.unet.has_cond
-        do_cfg = (guidance_scale > 1.0) and not has_cond
-        if do_cfg and negative_embeds is None:
-            raise LcmHipError("classifier-free guidance needs negative_embeds")
+        do_cfg = self._do_cfg(guidance_scale, negative_embeds)
         if self.unet.has_added and added is None:
             raise LcmHipError("this UNet needs added=(pooled_text_embeds [B,P], time_ids [B,6]) (SDXL text_time embedding)")
         passes = int(passes or 0)
@@ -826,9 +839,7 @@ self, prompt_embeds, seeds, width, height, steps, guidance_scale=1.0, negative_e
             if hint.dtype != torch.uint8 or tuple(hint.shape) != (B, height, width, 3):
                 raise LcmHipError(f"ControlNet hint must be uint8 [B={B}, H={height}, W={width}, 3], got {hint.dtype} {tuple(hint.shape)}")
         P = self.plan(B, h, w, steps, do_cfg, guidance_scale, lane=lane, refine=refine, control=cscale)
-        stream = P.lane.stream
-        with torch.cuda.stream(stream):
-            # ---- host-side request state -> device (outside the graph) ----
+        with torch.cuda.stream(P.lane.stream):       # latents= and the hint may be device tensors
             for b, s in enumerate(seeds):
                 if latents is not None:
                     P.h_lat[b].copy_(torch.as_tensor(latents[b]).reshape(4, h, w))
@@ -842,50 +853,25 @@ self, prompt_embeds, seeds, width, height, steps, guidance_scale=1.0, negative_e
                     P.h_lat[b].copy_(l0[0])
                 for i, n in enumerate(extra):
                     P.h_noise[i, b].copy_(n[0])
-            P.lat0.copy_(P.h_lat, non_blocking=True)
-            P.noise.copy_(P.h_noise, non_blocking=True)
             if hint is not None:
                 P.h_hint.copy_(hint)
+
+        def upload():
+            if hint is not None:
                 P.hint.copy_(P.h_hint, non_blocking=True)
             if refine is not None and refine[2]:
                 for b in range(B):
                     P.xk[0, b].copy_(start[1][b].reshape(4, h, w), non_blocking=True)
-            self._upload_text(P, pe, negative_embeds, guidance_scale)
             if self.unet.has_added:
-                def _add_rows(a):
-                    pooled, tids = a
-                    pooled = torch.as_tensor(pooled).to(torch.float32).reshape(B, -1).cpu()
-                    sin = sinusoid_host(np.asarray(tids, dtype=np.float32).reshape(-1), self.unet.cfg["addition_time_embed_dim"])
-                    return torch.cat([pooled, torch.from_numpy(sin).reshape(B, -1)], dim=1).to(torch.float16)
-                rows = _add_rows(added)
-                if do_cfg:
-                    neg_rows = _add_rows(negative_added if negative_added is not None else (torch.zeros(B, rows.shape[1] - 6 * self.unet.cfg["addition_time_embed_dim"]), added[1]))
-                    P.add_in[:B].copy_(neg_rows, non_blocking=True)
-                    P.add_in[B:].copy_(rows, non_blocking=True)
-                else:
-                    P.add_in.copy_(rows, non_blocking=True)
-            # ---- the sampler: eager once (allocates scratch), then captured + replayed ----
-            eager = (not self.use_graph) or taps is not None or want_float
-            if eager:
-                with self._build_lock:               # eager launches allocate scratch
-                    final = self._enqueue(P, guidance_scale, want_float=want_float, taps=taps)
-            else:
-                self._ensure_graph(P, guidance_scale)
-                P.graph.launch()
-                final = P.lat[B:] if do_cfg else P.lat
-            P.h_rgb.copy_(P.rgb, non_blocking=True)
-            P.h_pool8.copy_(P.pool8, non_blocking=True)
-            P.h_latout.copy_(final, non_blocking=True)
-            xk = P.xk.clone() if refine is not None else None
-            stream.synchronize()
-        out = dict(rgb=P.h_rgb.numpy().copy(), latents=P.h_latout.numpy().copy(), pool8=P.h_pool8.numpy().copy())
+                self._upload_added(P, added, negative_added)
+
+        out, xk = self._request([P], pe, negative_embeds, guidance_scale, upload, want_float=want_float, taps=taps,
+                                more=(lambda: P.xk.clone()) if refine is not None else None)
         if refine is not None:
             out["xk"], out["xk_first"] = xk, passes - refine[1]
             out["unet_evals"] = steps * (refine[1] + (0 if refine[2] else 1))
         if control is not None:
             out["controlnet_evals"] = steps
-        if want_float:
-            out["image"] = P.img_f32.cpu().numpy()   # NHWC float, pre-clamp
         return out
 
     # hot loop only (device resident inputs already in the plan): used by bench.py
