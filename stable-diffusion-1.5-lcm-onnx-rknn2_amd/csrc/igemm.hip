@@ -404,12 +404,12 @@ __global__ __launch_bounds__(256, S == 1 ? (BM + BN < 256 ? 4 : 3) : 2) void ige
             }
             if constexpr (ln) {
                 ln_finish<TM>(ln_s, ln_q, p.K, p.ln_eps);
-                igemm_epilogue<BM, BN>(p, acc, m_of, (nt0 + ni_cur) * BN + wn * (BN / 2), fq, z, slab_of, ln_s, ln_q, ln_lds, nt0 * BN);
+                igemm_epilogue<BM, BN, 0, (S >= 3)>(p, acc, m_of, (nt0 + ni_cur) * BN + wn * (BN / 2), fq, z, slab_of, ln_s, ln_q, ln_lds, nt0 * BN);
             } else if constexpr (EPI != 0) {       // (the launcher gives such a launch one n-tile per workgroup: the ring is dead here)
                 tile_epilogue_staged<BM, BN>(p, acc, m_of, (nt0 + ni_cur) * BN, wm, wn, fq, slab_of, smem,
                                              [&](int q) { return m_base + q < p.M ? m_base + q : -1; });
             } else {
-                igemm_epilogue<BM, BN>(p, acc, m_of, (nt0 + ni_cur) * BN + wn * (BN / 2), fq, z, slab_of);
+                igemm_epilogue<BM, BN, 0, (S >= 3)>(p, acc, m_of, (nt0 + ni_cur) * BN + wn * (BN / 2), fq, z, slab_of);
             }
             ++ni_cur;
 #pragma unroll
@@ -431,7 +431,7 @@ __global__ __launch_bounds__(256, S == 1 ? (BM + BN < 256 ? 4 : 3) : 2) void ige
             const int r = m_base + wm * (BM / 2) + bp * 32;
             slab_of[bp] = r < p.M ? (r >> 5) : -1;
         }
-        igemm_epilogue<BM, BN>(p, tot, m_of, nt0 * BN + wn * (BN / 2), fq, z, slab_of);
+        igemm_epilogue<BM, BN, 0, (S >= 3)>(p, tot, m_of, nt0 * BN + wn * (BN / 2), fq, z, slab_of);
     }
 }
 
@@ -458,6 +458,14 @@ __device__ __forceinline__ int reduce_pixel(const IgemmParams& p, int slab, int 
     return (bimg * p.rg_OH + y) * p.rg_OW + x;
 }
 
+// Every load of the wave -- bias, both fragments' row-add and residual, the slabs of both fragments in batches of RED_BATCH
+// -- is issued before the first addition, and no branch stands in front of a load: a fragment outside the problem reads row 0
+// and masks its store and its statistics.  The slabs were written by other XCDs, so every dependent load is an Infinity
+// Cache round trip at best; per-fragment loads behind `if (m < 0) continue` cost 1 + 2 (splits + 2) of them in a row, this
+// form 1 (+1 per further RED_BATCH slabs).  The additions and their order are unchanged: slab 0, += slab s in slab order,
+// + bias, + rowadd, * out_scale, + res, then fp16.  `res` may share storage with `out`: a lane reads only the elements it
+// later writes (the clamped read of a masked fragment is discarded), so reading early is safe.
+#define RED_BATCH 8
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(IgemmParams p, int total_slabs) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x & 63, ncg = p.N >> 4;
@@ -467,29 +475,66 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(IgemmParams p, int t
     const int l = lane & 15, fq = lane >> 4;
     const int n = cg * 16 + fq * 4;
     const long long slab_stride = (long long)p.M * p.N;
-    f4 bias4 = {0.f, 0.f, 0.f, 0.f};
-    if (p.bias) { h4 t = *reinterpret_cast<const h4*>(p.bias + n); bias4 = (f4){(float)t[0], (float)t[1], (float)t[2], (float)t[3]}; }
+    const int splits = p.splits;
+    int m[2];
+    bool live[2];
+    const float* src[2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const int mm = reduce_pixel(p, slab, b, l);
+        live[b] = mm >= 0;
+        m[b] = live[b] ? mm : 0;
+        src[b] = p.ws + (long long)m[b] * p.N + n;
+    }
+    f4 t[2][RED_BATCH];
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int k = 0; k < RED_BATCH; ++k)
+            if (k < splits) t[b][k] = *reinterpret_cast<const f4*>(src[b] + k * slab_stride);
+    h4 hb = {}, ha[2] = {}, hr[2] = {};
+    if (p.bias) hb = *reinterpret_cast<const h4*>(p.bias + n);
+    if (p.rowadd) {
+#pragma unroll
+        for (int b = 0; b < 2; ++b) ha[b] = *reinterpret_cast<const h4*>(p.rowadd + (long long)(m[b] / p.rows_per_batch) * p.ld_rowadd + n);
+    }
+    if (p.res) {
+#pragma unroll
+        for (int b = 0; b < 2; ++b) hr[b] = *reinterpret_cast<const h4*>(p.res + (long long)m[b] * p.ldr + n);
+    }
+    f4 v[2];
+    for (int s0 = 0;;) {
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int k = 0; k < RED_BATCH; ++k) {
+                if (s0 + k >= splits) continue;
+                if (k == 0 && s0 == 0) { v[b] = t[b][0]; continue; }
+                v[b][0] += t[b][k][0]; v[b][1] += t[b][k][1]; v[b][2] += t[b][k][2]; v[b][3] += t[b][k][3];
+            }
+        s0 += RED_BATCH;
+        if (s0 >= splits) break;
+#pragma unroll
+        for (int b = 0; b < 2; ++b)          // more than RED_BATCH parts (lcm_set_split_policy allows 64): the next whole batch
+#pragma unroll
+            for (int k = 0; k < RED_BATCH; ++k)
+                if (s0 + k < splits) t[b][k] = *reinterpret_cast<const f4*>(src[b] + (s0 + k) * slab_stride);
+    }
+    const f4 bias4 = {(float)hb[0], (float)hb[1], (float)hb[2], (float)hb[3]};      // null bias: +0.0f, as before
     float ssum[4] = {0.f, 0.f, 0.f, 0.f}, ssq[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-        const int m = reduce_pixel(p, slab, b, l);
-        if (m < 0) continue;
-        const float* src = p.ws + (long long)m * p.N + n;
-        f4 v = *reinterpret_cast<const f4*>(src);
-        for (int s = 1; s < p.splits; ++s) {
-            f4 t = *reinterpret_cast<const f4*>(src + s * slab_stride);
-            v[0] += t[0]; v[1] += t[1]; v[2] += t[2]; v[3] += t[3];
-        }
-        v[0] += bias4[0]; v[1] += bias4[1]; v[2] += bias4[2]; v[3] += bias4[3];
-        if (p.rowadd) { h4 t = *reinterpret_cast<const h4*>(p.rowadd + (long long)(m / p.rows_per_batch) * p.ld_rowadd + n);
-            v[0] += (float)t[0]; v[1] += (float)t[1]; v[2] += (float)t[2]; v[3] += (float)t[3]; }
-        v[0] *= p.out_scale; v[1] *= p.out_scale; v[2] *= p.out_scale; v[3] *= p.out_scale;
-        if (p.res) { h4 t = *reinterpret_cast<const h4*>(p.res + (long long)m * p.ldr + n);
-            v[0] += (float)t[0]; v[1] += (float)t[1]; v[2] += (float)t[2]; v[3] += (float)t[3]; }
-        h4 o = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
-        *reinterpret_cast<h4*>(p.out + (long long)m * p.ldo + n) = o;
+        f4 w = v[b];
+        w[0] += bias4[0]; w[1] += bias4[1]; w[2] += bias4[2]; w[3] += bias4[3];
+        if (p.rowadd) { w[0] += (float)ha[b][0]; w[1] += (float)ha[b][1]; w[2] += (float)ha[b][2]; w[3] += (float)ha[b][3]; }
+        w[0] *= p.out_scale; w[1] *= p.out_scale; w[2] *= p.out_scale; w[3] *= p.out_scale;
+        if (p.res) { w[0] += (float)hr[b][0]; w[1] += (float)hr[b][1]; w[2] += (float)hr[b][2]; w[3] += (float)hr[b][3]; }
+        h4 o = {(half_t)w[0], (half_t)w[1], (half_t)w[2], (half_t)w[3]};
+        if (live[b]) {
+            *reinterpret_cast<h4*>(p.out + (long long)m[b] * p.ldo + n) = o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { const float f = (float)o[j]; ssum[j] += f; ssq[j] += f * f; }
+            for (int j = 0; j < 4; ++j) { const float f = (float)o[j]; ssum[j] += f; ssq[j] += f * f; }
+        }
     }
     if (p.stats) {
 row16_sum8(ssum, ssq);

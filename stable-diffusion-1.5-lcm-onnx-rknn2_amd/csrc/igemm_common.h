@@ -117,7 +117,15 @@ __device__ __forceinline__ int stage_src(int cpos, int q) { return (cpos + CH - 
 // STAGED = 1: the residual tile is READ from, and the result tile WRITTEN to, an LDS image of the output tile (`stage`, BM x BN
 // fp16, stage_pos layout; tile_epilogue_staged fills it by LDS-DMA beforehand and copies it out in whole rows afterwards) instead
 // of global memory in 8-byte pieces per lane.  The arithmetic is this one function either way.
-template <int BM, int BN, int STAGED = 0>
+// BATCHED = 1 (ring kernels with the 256-VGPR budget, non-staged form): the bias, row-add and residual operands of a whole
+// batch of fragments (the tile, or one n-fragment of a large tile) are loaded before the first of them is used, and the
+// per-fragment code has no branch in front of its loads (a row outside the problem reads row 0 and masks its store and its
+// statistics), so the wave makes ONE memory round trip per batch where the per-fragment form makes up to 1 + 2 per fragment,
+// each behind its own s_waitcnt vmcnt(0).  None of the
+// operands depends on the accumulators; the additions and their order are unchanged.  The residual may share storage with the
+// output: a lane reads exactly the elements it later writes (the clamped reads of masked lanes are discarded), so reading
+// early is safe.
+template <int BM, int BN, int STAGED = 0, int BATCHED = 0>
 __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f4 (&acc)[BN / 32][BM / 32], const int (&m_of)[BM / 32],
                                                int n_wave, int fq, int z, const int (&slab_of)[BM / 64],
                                                const float* ln_mu = nullptr, const float* ln_r = nullptr,
@@ -159,11 +167,48 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f4 (&acc)[B
     const bool do_stats = p.stats != nullptr && p.epi == 0;
     const int lane = threadIdx.x & 63;
     if (p.epi != 1) {
+        constexpr bool PRE = BATCHED != 0 && STAGED == 0;
+        // n-fragments per batch: the whole tile while that costs at most 20 VGPRs (up to four fragments: the 64 x 64 tiles of the
+        // batch-1 pass), else one n-fragment with all its m-fragments (2 + 4 TM VGPRs) -- the large tiles run near their budget
+        constexpr int NB = PRE ? (TM * TN <= 4 ? TN : 1) : 1;
+        h4 pre_bias[NB], pre_add[NB][PRE ? TM : 1], pre_res[NB][PRE ? TM : 1];
+        int mc[TM];
+#pragma unroll
+        for (int b = 0; b < TM; ++b) mc[b] = m_of[b] < 0 ? 0 : m_of[b];
 #pragma unroll
         for (int a = 0; a < TN; ++a) {
             const int n = n_wave + a * 16 + fq * 4;
+            if constexpr (PRE) {
+                if (a % NB == 0) {
+                    if (p.bias) {
+#pragma unroll
+                        for (int i = 0; i < NB; ++i) pre_bias[i] = *reinterpret_cast<const h4*>(p.bias + n + i * 16);
+                    }
+                    if (p.rowadd) {
+#pragma unroll
+                        for (int b = 0; b < TM; ++b) {
+                            const half_t* row = p.rowadd + (long long)(mc[b] / p.rows_per_batch) * p.ld_rowadd + n;
+#pragma unroll
+                            for (int i = 0; i < NB; ++i) pre_add[i][b] = *reinterpret_cast<const h4*>(row + i * 16);
+                        }
+                    }
+                    if (p.res) {
+#pragma unroll
+                        for (int b = 0; b < TM; ++b) {
+                            const half_t* row = p.res + (long long)mc[b] * p.ldr + n;
+#pragma unroll
+                            for (int i = 0; i < NB; ++i) pre_res[i][b] = *reinterpret_cast<const h4*>(row + i * 16);
+                        }
+                    }
+                }
+            }
             f4 bias4 = {0.f, 0.f, 0.f, 0.f};
-            if (p.bias) { h4 t = *reinterpret_cast<const h4*>(p.bias + n); bias4 = (f4){(float)t[0], (float)t[1], (float)t[2], (float)t[3]}; }
+            if (p.bias) {
+                h4 t;
+                if constexpr (PRE) t = pre_bias[a % NB];
+                else t = *reinterpret_cast<const h4*>(p.bias + n);
+                bias4 = (f4){(float)t[0], (float)t[1], (float)t[2], (float)t[3]};
+            }
             f4 lng4 = {0.f, 0.f, 0.f, 0.f}, lnc4 = {0.f, 0.f, 0.f, 0.f};
             if (ln_mu) {
                 if (ln_lds) { lng4 = *reinterpret_cast<const __attribute__((address_space(3))) f4*>(ln_lds + (n - n_tile0));
@@ -176,14 +221,18 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f4 (&acc)[B
 #pragma unroll
                 for (int b = 2 * bp; b < 2 * bp + 2; ++b) {
                     const int m = m_of[b];
-                    if (m < 0) continue;
+                    if constexpr (!PRE) { if (m < 0) continue; }
+                    const bool live = m >= 0;          // PRE: rows outside the problem run the arithmetic on row 0's operands, unstored
                     f4 v = acc[a][b];
                     if (ln_mu) {
 #pragma unroll
                         for (int j = 0; j < 4; ++j) v[j] = __builtin_fmaf(ln_r[b], __builtin_fmaf(-ln_mu[b], lng4[j], v[j]), lnc4[j]);
                     }
                     v[0] += bias4[0]; v[1] += bias4[1]; v[2] += bias4[2]; v[3] += bias4[3];
-                    if (p.rowadd) { h4 t = *reinterpret_cast<const h4*>(p.rowadd + (long long)(m / p.rows_per_batch) * p.ld_rowadd + n);
+                    if (p.rowadd) {
+                        h4 t;
+                        if constexpr (PRE) t = pre_add[a % NB][b];
+                        else t = *reinterpret_cast<const h4*>(p.rowadd + (long long)(m / p.rows_per_batch) * p.ld_rowadd + n);
                         v[0] += (float)t[0]; v[1] += (float)t[1]; v[2] += (float)t[2]; v[3] += (float)t[3]; }
                     v[0] *= p.out_scale; v[1] *= p.out_scale; v[2] *= p.out_scale; v[3] *= p.out_scale;
                     if (p.epi == 2) {          // quick_gelu: x * sigmoid(1.702 x)   (CLIP text encoder MLP)
@@ -201,12 +250,13 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f4 (&acc)[B
                     if (p.res) {
                         h4 t;
                         if constexpr (STAGED != 0) t = *reinterpret_cast<const h4*>(stage + soff);
+                        else if constexpr (PRE) t = pre_res[a % NB][b];
                         else t = *reinterpret_cast<const h4*>(p.res + (long long)m * p.ldr + n);
                         v[0] += (float)t[0]; v[1] += (float)t[1]; v[2] += (float)t[2]; v[3] += (float)t[3]; }
                     h4 o = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
                     if constexpr (STAGED != 0) *reinterpret_cast<h4*>(stage + soff) = o;
-                    else *reinterpret_cast<h4*>(outb + (long long)m * p.ldo + n) = o;
-                    if (do_stats) {
+                    else if (live) *reinterpret_cast<h4*>(outb + (long long)m * p.ldo + n) = o;
+                    if (do_stats && live) {
 #pragma unroll
                         for (int j = 0; j < 4; ++j) { const float f = (float)o[j]; ssum[j] += f; ssq[j] += f * f; }
                     }

@@ -167,8 +167,9 @@ __global__ __launch_bounds__(64) void gn_finalize_affine_kernel(const float* __r
 // GroupNorm statistics of one (image, group) from the per-channel partial statistics the producing contraction kernel
 // wrote in its epilogue (csrc/igemm_common.h): stats[(b*P + p)][C][2].  The group's channels may span both sources of a
 // fused concat.  ONE routine for the finalize kernel and the single-launch kernel below (which of the two runs depends on
-// the tensor size, hence on the batch: they must agree bit for bit).  Fixed order: thread-sequential over slabs (4 in
-// flight), wave butterfly, then the 4 wave sums in wave order.  `red` = 8 floats of LDS.  Returns (mean, rstd) to every thread.
+// the tensor size, hence on the batch: they must agree bit for bit).  Fixed order: thread-sequential over slabs (GN_SB
+// in flight), wave butterfly, then the 4 wave sums in wave order.  `red` = 8 floats of LDS.  Returns (mean, rstd) to every thread.
+#define GN_SB 8
 __device__ __forceinline__ float2 gn_group_stats(const float* __restrict__ st1, int P1, int C1, const float* __restrict__ st2, int P2,
                                                  int C2, int b, int c_lo, int c_hi, float inv_count, float eps, float* red) {
     const int tid = threadIdx.x;
@@ -180,18 +181,29 @@ __device__ __forceinline__ float2 gn_group_stats(const float* __restrict__ st1, 
         if (sl >= spl) return;
         const float* base = st + ((long long)b * P * Cs + a + jc) * 2;
         const long long stride = (long long)Cs * 2;
-        int pp = sl;
-        for (; pp + 3 * spl < P; pp += 4 * spl) {
-            const float2 v0 = *reinterpret_cast<const float2*>(base + pp * stride);
-            const float2 v1 = *reinterpret_cast<const float2*>(base + (pp + spl) * stride);
-            const float2 v2 = *reinterpret_cast<const float2*>(base + (pp + 2 * spl) * stride);
-            const float2 v3 = *reinterpret_cast<const float2*>(base + (pp + 3 * spl) * stride);
-            s += (v0.x + v1.x) + (v2.x + v3.x);
-            q += (v0.y + v1.y) + (v2.y + v3.y);
-        }
-        for (; pp < P; pp += spl) {
-            const float2 v = *reinterpret_cast<const float2*>(base + pp * stride);
-            s += v.x; q += v.y;
+        // GN_SB slabs per round, every load of a round issued before its first addition (indices past the end are clamped to
+        // the last slab and their values dropped): one memory round trip per round where a loop of quads and then of single
+        // slabs made one per iteration.  The additions are those of that loop, in its order: whole quads as
+        // (v0 + v1) + (v2 + v3) while four slabs remain, then the rest one by one.
+        for (int pp = sl; pp < P; pp += GN_SB * spl) {
+            float2 v[GN_SB];
+#pragma unroll
+            for (int k = 0; k < GN_SB; ++k) v[k] = *reinterpret_cast<const float2*>(base + min(pp + k * spl, P - 1) * stride);
+#pragma unroll
+            for (int g = 0; g < GN_SB; g += 4) {     // both forms computed, one selected: a branch here would leave loads of the
+                const int p0 = pp + g * spl;         // round unconsumed on some paths, and the compiler then waits at the loop head
+                const float sf = s + ((v[g].x + v[g + 1].x) + (v[g + 2].x + v[g + 3].x));
+                const float qf = q + ((v[g].y + v[g + 1].y) + (v[g + 2].y + v[g + 3].y));
+                float s1 = s, q1 = q;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const bool in = p0 + k * spl < P;
+                    const float ts = s1 + v[g + k].x, tq = q1 + v[g + k].y;
+                    s1 = in ? ts : s1; q1 = in ? tq : q1;
+                }
+                const bool full = p0 + 3 * spl < P;
+                s = full ? sf : s1; q = full ? qf : q1;
+            }
         }
     };
     accumulate(st1, P1, C1, c_lo, min(c_hi, C1) - c_lo);                       // channels of the group in source 1
@@ -227,8 +239,13 @@ __global__ __launch_bounds__(256) void gn_finalize_from_stats_kernel(const float
 // at the ~3 us launch floor each: workgroup (pixel slice, image, group) re-derives its group's mean / rstd from the
 // producer statistics -- P * cpg * 8 bytes out of L2, cheap to repeat per slice -- and applies the affine (+SiLU) to its
 // slice of pixels for the group's cpg channels.  Same arithmetic as the two-launch path.  The first GN_PRE activation
-// pairs of every thread are fetched BEFORE the statistics are reduced: the two dependent memory round trips of the kernel
-// (statistics, then activations) overlap instead of adding up (the kernel is pure latency at these sizes).
+// pairs of every thread and its gamma / beta are fetched BEFORE the statistics are reduced, so that the kernel's dependent
+// memory round trips (activations | statistics) overlap instead of adding up (the kernel is pure latency at these sizes).
+// For that the early loads must have no branch in front of them: the item index is clamped (slots past the slice re-read
+// its last item and are never stored) and the concat source is chosen by ADDRESS, not by loading under `c < C1 ? x : x2`
+// (x2 is null when C2 == 0 and then never selected).  With the branches, the compiler put an s_waitcnt vmcnt(0) behind
+// every one of the GN_PRE loads and the overlap never happened.  Checked in the gfx950 assembly (tools/load_chains.py;
+// tests/test_load_chains_cpu.py fails if a wait reappears between the first activation load and the first statistics load).
 typedef _Float16 h2v __attribute__((ext_vector_type(2)));
 #define GN_PRE 6
 __global__ __launch_bounds__(256) void gn_from_stats_fused_kernel(const half_t* __restrict__ x, int C1, const half_t* __restrict__ x2, int C2,
@@ -250,21 +267,27 @@ __global__ __launch_bounds__(256) void gn_from_stats_fused_kernel(const half_t* 
         const int pr = i / hp, j = i - pr * hp;
         const int c = c_lo + 2 * j;
         const long long row = rowbase + r0 + pr;
-        return (c < C1) ? *reinterpret_cast<const h2v*>(x + row * C1 + c) : *reinterpret_cast<const h2v*>(x2 + row * C2 + (c - C1));
+        const bool first = c < C1;
+        const half_t* src = first ? x : x2;
+        const int ld = first ? C1 : C2, cc = first ? c : c - C1;
+        return *reinterpret_cast<const h2v*>(src + row * ld + cc);
     };
     h2v pre[GN_PRE];
 #pragma unroll
-    for (int k = 0; k < GN_PRE; ++k) {
-        const int i = tid + 256 * k;
-        pre[k] = (i < items) ? load_item(i) : (h2v){(half_t)0, (half_t)0};
-    }
+    for (int k = 0; k < GN_PRE; ++k) pre[k] = load_item(min(tid + 256 * k, items - 1));
+    const int cgb = c_lo + min(tid, cpg - 1);
+    const half_t gam = gamma[cgb], bet = beta[cgb];
     const float2 mr = gn_group_stats(st1, P1, C1, st2, P2, C2, b, c_lo, c_lo + cpg, inv_count, eps, red);
     if (tid < cpg) {
-        const float a = mr.y * (float)gamma[c_lo + tid];
+        const float a = mr.y * (float)gam;
         sc_s[tid] = a;
-        sh_s[tid] = (float)beta[c_lo + tid] - mr.x * a;
+        sh_s[tid] = (float)bet - mr.x * a;
     }
     __syncthreads();
+    // the prefetched pairs are consumed HERE, once, in straight-line code: used first inside the divergent `i < items` blocks
+    // below, each block gets a conservative s_waitcnt vmcnt(0) of its own, which also waits for the previous block's store
+#pragma unroll
+    for (int k = 0; k < GN_PRE; ++k) asm volatile("" : "+v"(pre[k]));
     auto apply_store = [&](int i, h2v v) {
         const int pr = i / hp, j = i - pr * hp;
         const int c = c_lo + 2 * j;
