@@ -384,14 +384,62 @@ def c4_input(lat, pre_w, pre_b, in_scale):
 
 
 # ---- attention ---------------------------------------------------------------------------------------------------------
-def attention_check(got, q, k, v, B, heads, Sq, Sk, d, *, scale, causal=False, images=None, chunk_bytes=1 << 29):
-    """softmax(Q K^T * scale) V in fp64 (scale <= 0: Q carries scale * log2 e, the logits are base-2).  Bound: the logits are
-    off by at most D = scale * (H + C_ACC U sqrt(d)) * max_j sum_i |q_i k_ji| (Q pre-scaled in fp16, fp32 accumulation), which
-    moves each unnormalised probability by a factor within exp(+-D); P is rounded to fp16 for the PV product; the online
-    rescales are Sk / 32 fp32 multiplications at most.  Hence
-        |o - o_ref| <= (2 (e^(2D) - 1) + 2 H + (2 C_ACC sqrt(Sk) + Sk / 32 + 8) U) * sum_j p_j |v_j|  (+ the fp16 store)."""
+P_SUBNORMAL = 14.0      # a probability more than 2^-14 below its row's largest may be stored as an fp16 subnormal
+
+
+def attention_kernel(d, Sk, causal):
+    """which kernel of csrc/attention.hip serves a call (lcm_attention_f16, default switches): "attn2" the streaming kernel of
+    the long non-causal sequences, "wide" the d = 512 kernel, "attn" the register-staged kernel of everything else."""
+    if not causal and Sk >= 128 and d in (40, 64, 80):
+        return "attn2"
+    return "wide" if d == 512 else "attn"
+
+
+def attention_tile(d, Sk, causal):
+    """keys per K/V tile of the kernel that serves the call"""
+    return 32 if attention_kernel(d, Sk, causal) == "wide" else 64
+
+
+def attention_key_split(d, Sk, causal):
+    """True where the streaming kernel splits the keys of a query block over two wave groups (launch_attn2, default switches):
+    tiles [0, ceil(n / 2)) and [ceil(n / 2), n)."""
+    return attention_kernel(d, Sk, causal) == "attn2" and 1024 <= Sk <= 4096
+
+
+def attention_rounds_q(d, Sk, causal, scale):
+    """True where the launch rounds a SCALED Q to fp16: the streaming kernel called with scale > 0 (x = (half)(x * sc)).  With
+    scale <= 0 it multiplies by 1.0 (exact); the other two kernels multiply the fp32 accumulator by the scale."""
+    return scale > 0 and attention_kernel(d, Sk, causal) == "attn2"
+
+
+def attention_check(got, q, k, v, B, heads, Sq, Sk, d, *, scale, causal=False, images=None, chunk_bytes=1 << 29, q_rounded=None):
+    """softmax(Q K^T * scale) V in fp64 (scale <= 0: Q carries scale * log2 e, the logits are base-2).  Bound, per query row.
+
+    Logits.  With A = max_j sum_i |q_i k_ji| * scale and |L| = max_j |logit_j| (natural units) a logit is off by at most
+        D = (h_q + C_ACC U sqrt(d)) A + 4 U |L|
+    h_q = H where the launch rounds the scaled Q to fp16 (attention_rounds_q: the streaming kernel with scale > 0), else 0:
+    nothing is rounded before the fp32 accumulation.  The predicate assumes the default switches; under set_attention_impl(0) or
+    2 forced waves the register-staged kernel serves those shapes and rounds nothing, so the predicate errs towards the looser
+    bound, never the tighter.  q_rounded overrides it (tests/test_launch_audit.py: what the term hides where it does not belong).
+    C_ACC U sqrt(d) A is that accumulation.  4 U |L| covers the fp32 roundings of s * sc and s - m (at most 3 U |L|, |s - m| <=
+    2 |L|) and, in the d = 40 streaming form, the running max carried in the QK^T MFMA as an fp16 (hi, lo) split of -m: hi + lo
+    is -m to 2^-22 |m| = 4 U |m|; the tile that moves the max subtracts the exact fp32 delta while every later tile sees the
+    split, so the two disagree by up to 2^-22 |m| with |m| <= |L| (base-2 units need |m| < 65504, the fp16 range of hi).
+    D moves each unnormalised probability by a factor within exp(+-D).
+
+    P is rounded to fp16 for the PV product (the streaming kernel defers its rescale, so P <= 2^8: still H relative); the
+    online rescales are Sk / 32 fp32 multiplications at most; O and l accumulate in fp32:
+        E = (2 (e^(2D) - 1) + 2 H + (2 C_ACC sqrt(Sk) + Sk / 32 + 8) U) * sum_j p_j |v_j| + E_sub
+    E_sub, the fp16-subnormal range of P.  In the units of the running max at its tile the largest P so far is >= 1 (the max
+    never exceeds the largest score seen), so l >= 1 from there on and later rescales multiply P's error and l alike by a
+    factor <= 1.  A key whose score is within 2^-14 of the row's largest has P >= 2^-14, a normal fp16.  Every other unmasked key
+    (set J) is off by at most SUB absolute -- also when it flushes to 0 -- which moves the numerator by SUB sum_J |v_j| and l by
+    SUB |J|:
+        E_sub = SUB (sum_J |v_j| + |J| |o|)
+    then the fp16 store (store_bound)."""
     dev = got.device
     s = LN2 if scale <= 0 else scale
+    h_q = H if (attention_rounds_q(d, Sk, causal, scale) if q_rounded is None else q_rounded) else 0.0
     worst = 0.0
     for b in (range(B) if images is None else images):
         for hh in range(heads):
@@ -411,9 +459,10 @@ def attention_check(got, q, k, v, B, heads, Sq, Sk, d, *, scale, causal=False, i
                 P = torch.softmax(L, 1)
                 o = P @ V
                 pv = P @ V.abs()
-                D = (H + C_ACC * U * math.sqrt(d)) * La.max(1, keepdim=True).values + 4 * U * L.abs().nan_to_num(0, 0, 0).max(1, keepdim=True).values
+                D = (h_q + C_ACC * U * math.sqrt(d)) * La.max(1, keepdim=True).values + 4 * U * L.abs().nan_to_num(0, 0, 0).max(1, keepdim=True).values
                 rel = 2 * torch.expm1(2 * D) + 2 * H + (2 * C_ACC * math.sqrt(Sk) + Sk / 32 + 8) * U
-                E = rel * pv
+                J = (torch.isfinite(L) & (L < L.max(1, keepdim=True).values - P_SUBNORMAL * LN2)).to(torch.float64)
+                E = rel * pv + SUB * (J @ V.abs() + J.sum(1, keepdim=True) * o.abs())
                 worst = max(worst, worst_ratio(got[b * Sq + r0:b * Sq + r1, cs], o, store_bound(o, E)))
     return worst
 
@@ -800,6 +849,14 @@ def out_window(out, rows, cols, ld, batch=1, stride_o=0):
 
 def window_of(t, start, length):
     return t.as_strided((length,), (1,), start)
+
+
+def frame_writes(before, after, view):
+    """number of elements of a whole buffer OUTSIDE the strided ``view`` into it whose bits changed (``before``: the buffer
+    cloned ahead of the launch): rows in front of and behind the output as well as the gap columns."""
+    keep = torch.ones(after.numel(), dtype=torch.bool, device=after.device)
+    keep.as_strided(view.shape, view.stride(), view.storage_offset() - after.storage_offset()).fill_(False)
+    return stray_writes(before.reshape(-1), after.reshape(-1), keep)
 
 
 def stray_writes(before, after, keep):

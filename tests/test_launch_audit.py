@@ -1,9 +1,13 @@
 """The launch audit's error bound (tests/launch_audit.py) on the CPU: a product computed the way the kernels compute it (fp16
 operands, fp32 accumulation over the k-tiles of each part of the K partition, parts added in order, fp16 store) passes it;
 the same product wrong by one K term, one 64-wide K chunk, one output row or a skipped prologue SiLU does not.  Without this a
-bound could grow loose enough to accept anything."""
+bound could grow loose enough to accept anything.  The same for attention: the online softmax of each attention kernel replayed
+over the designed logits of tests/attention_cases.py stays inside attention_check, and each of nine planted faults leaves it."""
+import numpy as np
+import pytest
 import torch
 
+import attention_cases as ac
 import launch_audit as la
 
 
@@ -468,6 +472,235 @@ def test_attention_bound_rejects_a_padding_key_and_a_dropped_last_key():
         assert chk(_attn_kernel_like(q, k, v, scale)) <= 1.0, Sk
         assert chk(_attn_kernel_like(q, k, v, scale, extra_zero_key=True)) > 1.0, ("a zero padding key admitted", Sk)
         assert chk(_attn_kernel_like(q, k, v, scale, drop_last=True)) > 1.0, ("the last real key dropped", Sk)
+
+
+# ---- the online softmax of csrc/attention.hip, replayed ----------------------------------------------------------------
+# fault -> the kernel families (attention_cases.Case.family) whose code has the step the fault breaks
+ATTN_FAULTS = {
+    "o_not_rescaled": ("attn", "attn_causal", "attn2", "wide"),       # O keeps its old unit when the running max moves
+    "l_not_rescaled": ("attn", "attn_causal", "attn2", "wide"),       # forms whose row sum is a register (no ONES row in O^T)
+    "fold_lo_dropped": ("attn2",),                                    # d = 40: only the fp16 hi part of -m enters the MFMA
+    "delta_not_clamped": ("attn2",),                                  # a lane below its max follows the wave's rescale downwards
+    "p_clamped_at_1": ("attn2",),                                     # P of the deferred rescale reaches 2^THR
+    "last_key_masked": ("attn", "attn_causal", "attn2", "wide"),
+    "padding_key_admitted": ("attn", "attn2", "wide"),
+    "diagonal_masked": ("attn_causal",),
+    "merge_without_a2": ("attn2",),                                   # key split: group 1's state added without 2^(m2 - m)
+}
+
+
+def _attn_replay(q, k, v, *, tile=64, thr=None, fold=False, ones=False, ksplit=False, causal=False, sc=1.0, wave=32,
+                 pad="zero", fault=None):
+    """One head the way the kernels compute it: fp32 logits of the fp16 operands per key tile, the running max / row sum / O
+    recurrence in fp32, P rounded to fp16 for the PV product, fp32 PV, fp16 store.
+      thr None: the max moves on every increase, P = exp2(s * sc - m) (attn_kernel, attn_wide_kernel);
+      thr: Q is scaled and rounded to fp16 first, the max moves (for the lanes of a `wave`-row wave together) only when one of
+        them grows by more than thr, each lane by its own max(grow, 0) (attn2_kernel); fold: -m enters the logit as fp16 hi + lo;
+      ones: the row sum accumulates the fp16 P (a row of O^T), else the fp32 P;
+      ksplit: tiles [0, ceil(n/2)) and [ceil(n/2), n) as two independent states, merged at the end;
+      pad: the rows of a ragged tile past Sk are zeros ("zero") or repeat the last key ("dup") before they are masked."""
+    Sq, Sk = q.shape[0], k.shape[0]
+    f32 = torch.float32
+    sc32 = torch.tensor(sc, dtype=f32)
+    Q = (q.float() * sc32).half().float() if thr is not None else q.float()
+    K, V = k.float(), v.float()
+    n = (Sk + tile - 1) // tile
+    rows = torch.arange(Sq)
+
+    def any_wave(t):
+        w = torch.nn.functional.pad(t.float(), (0, -Sq % wave)).view(-1, wave).sum(1) > 0
+        return w.repeat_interleave(wave)[:Sq]
+
+    def stream(t0, t1):
+        m = torch.zeros(Sq) if thr is not None else torch.full((Sq,), -1.0e30)
+        l, O = torch.zeros(Sq), torch.zeros(Sq, V.shape[1])
+        hi = lo = torch.zeros(Sq)
+        for it, t in enumerate(range(t0, t1)):
+            keys = torch.arange(t * tile, (t + 1) * tile)
+            src = keys.clamp(max=Sk - 1)
+            Kt, Vt = K[src], V[src]
+            if pad == "zero":
+                Kt, Vt = Kt * (keys < Sk)[:, None], Vt * (keys < Sk)[:, None]
+            S = Q @ Kt.T
+            if fold:
+                S = (S.double() + hi.double()[:, None] + lo.double()[:, None]).float()
+            limit = Sk + 1 if fault == "padding_key_admitted" and Sk % tile else Sk - 1 if fault == "last_key_masked" else Sk
+            masked = (keys >= limit)[None, :].expand(Sq, -1)
+            if causal:
+                masked = masked | ((keys[None, :] >= rows[:, None]) if fault == "diagonal_masked" else (keys[None, :] > rows[:, None]))
+            S = torch.where(masked, torch.tensor(-1.0e30), S)
+            mt = S.max(1).values
+            if thr is None:
+                m_new = torch.maximum(m, mt * sc32)
+                alpha = torch.exp2(m - m_new)
+                m = m_new
+                P = torch.exp2(S * sc32 - m[:, None])
+            else:
+                grow = mt if fold else mt - m
+                if it == 0:
+                    trig, delta, alpha = torch.ones(Sq, dtype=torch.bool), grow, torch.ones(Sq)
+                else:
+                    trig = any_wave(grow > thr)
+                    delta = torch.where(trig, grow if fault == "delta_not_clamped" else grow.clamp(min=0.0), torch.zeros(Sq))
+                    alpha = torch.exp2(-delta)
+                m = m + delta
+                if fold:
+                    S = S - delta[:, None]
+                    nhi = (-m).half().float()
+                    nlo = torch.zeros(Sq) if fault == "fold_lo_dropped" else (-m - nhi).half().float()
+                    hi, lo = torch.where(trig, nhi, hi), torch.where(trig, nlo, lo)
+                P = torch.exp2(S if fold else S - m[:, None])
+                if fault == "p_clamped_at_1":
+                    P = P.clamp(max=1.0)
+            if fault != "l_not_rescaled":
+                l = l * alpha
+            if fault != "o_not_rescaled":
+                O = O * alpha[:, None]
+            P16 = P.half().float()
+            l = l + (P16 if ones else P).sum(1)
+            O = O + P16 @ Vt
+        return m, l, O
+
+    if ksplit:
+        nh = (n + 1) // 2
+        (m1, l1, O1), (m2, l2, O2) = stream(0, nh), stream(nh, n)
+        m = torch.maximum(m1, m2)
+        a1 = torch.exp2(m1 - m)
+        a2 = torch.ones(Sq) if fault == "merge_without_a2" else torch.exp2(m2 - m)
+        l, O = l1 * a1 + l2 * a2, O1 * a1[:, None] + O2 * a2[:, None]
+    else:
+        _, l, O = stream(0, n)
+    return (O * (1.0 / l)[:, None]).half()
+
+
+def _replay_case(case, ops, fault=None):
+    """the whole case through the replay of the kernel that serves it -> [Sq, heads * d] fp16"""
+    q, k, v = ops
+    d, kern = case.d, case.kernel
+    sc = float(np.float32(case.scale) * np.float32(1.4426950408889634)) if case.scale > 0 else 1.0
+    kw = dict(tile=case.tile, causal=case.causal, sc=sc, fault=fault)
+    if kern == "attn2":
+        kw.update(thr=ac.THR, fold=d == 40, ones=d in (40, 80), ksplit=case.ksplit, pad="dup")
+    elif kern == "wide":
+        kw.update(wave=16, pad="dup")
+    else:
+        kw.update(ones=d in (40, 80))
+    return torch.cat([_attn_replay(*(t[:, h * d:(h + 1) * d] for t in (q, k, v)), **kw) for h in range(case.heads)], 1)
+
+
+def _case_ratio(case, ops, got):
+    q, k, v = ops
+    return la.attention_check(got, q, k, v, 1, case.heads, case.Sq, case.Sk, case.d, scale=case.scale, causal=case.causal)
+
+
+def _fault_applies(fault, case):
+    if case.family not in ATTN_FAULTS[fault]:
+        return False
+    if fault == "l_not_rescaled":
+        return case.d not in (40, 80) or case.kernel == "wide"
+    if fault == "fold_lo_dropped":
+        return case.d == 40
+    if fault == "merge_without_a2":
+        return case.ksplit
+    if fault == "padding_key_admitted":
+        return case.Sk % case.tile != 0
+    return True
+
+
+@pytest.fixture(scope="module")
+def attention_table():
+    return [(c, c.operands()) for c in ac.table()]
+
+
+def test_attention_replay_is_within_the_bound_on_every_designed_case(attention_table):
+    """The faithful replay of each kernel's recurrence stays inside attention_check on every case of tests/attention_cases.py:
+    the condition under which the GPU test may demand the same of the kernels.  Prints the worst ratio per kernel form."""
+    worst = {}
+    for case, ops in attention_table:
+        got = _replay_case(case, ops)
+        assert torch.isfinite(got.float()).all(), case.name
+        r = _case_ratio(case, ops, got)
+        worst[case.form] = max(worst.get(case.form, 0.0), r)
+        assert r <= 1.0, (case.name, r)
+    print("\n".join(f"replay worst ratio  {f:24s} {r:.3f}" for f, r in sorted(worst.items())))
+
+
+@pytest.mark.parametrize("fault", sorted(ATTN_FAULTS))
+def test_attention_cases_reject_a_planted_fault(attention_table, fault):
+    """every planted fault leaves the bound on at least one designed case of each kernel family whose code has that step"""
+    caught = {fam: None for fam in ATTN_FAULTS[fault]}
+    for case, ops in attention_table:
+        if caught.get(case.family, True) is not None or not _fault_applies(fault, case):
+            continue
+        r = _case_ratio(case, ops, _replay_case(case, ops, fault))
+        if r > 1.0:
+            caught[case.family] = (case.name, r)
+    assert all(caught.values()), (fault, caught)
+    print("\n".join(f"{fault:22s} {fam:12s} rejected by {c[0]} at {c[1]:.3g}" for fam, c in sorted(caught.items())))
+
+
+def test_dropped_fold_lo_is_rejected_on_every_large_offset_case(attention_table):
+    """The fp16 lo half of the folded max is what the +-1000.5 offsets are for: dropping it must leave the bound on each d = 40
+    streaming case that carries them below 4160 keys, not on one alone.  (At 330 keys the margin is 1.6x: the one to watch when a
+    derived term is added to attention_check; the key-split shapes stand at 5x.)"""
+    names = ("s40-96x330-offsets", "s40-96x1030-offsets", "s40-96x1088-offsets")
+    seen = 0
+    for case, ops in attention_table:
+        if case.name in names:
+            seen += 1
+            r = _case_ratio(case, ops, _replay_case(case, ops, "fold_lo_dropped"))
+            assert r > 1.0, (case.name, r)
+    assert seen == len(names)
+
+
+def test_frame_writes_counts_a_row_past_the_output():
+    """the layout of tests/test_attention_stress_gpu.py: out at column 8 of a wider pitch between two sentinel rows.  A row
+    stored past the last one (a lost `qrow < Sq` guard) or in front of the first lands outside launch_audit.out_window; the
+    whole-buffer comparison counts every element of it."""
+    rows, C, pad = 70, 80, 16
+    ldo = C + pad
+    buf = torch.full(((rows + 2) * ldo,), -7.0, dtype=torch.float16)
+    out = buf.as_strided((rows, C), (ldo, 1), ldo + pad // 2)
+    before = buf.clone()
+    out.fill_(1.0)
+    assert la.frame_writes(before, buf, out) == 0
+    buf.as_strided((1, C), (ldo, 1), (rows + 1) * ldo + pad // 2).fill_(2.0)          # row `rows`
+    assert la.frame_writes(before, buf, out) == C
+    buf.as_strided((1, C), (ldo, 1), pad // 2).fill_(2.0)                             # row -1
+    assert la.frame_writes(before, buf, out) == 2 * C
+    buf[ldo + pad // 2 + C] = 3.0                                                     # a gap column of row 0
+    assert la.frame_writes(before, buf, out) == 2 * C + 1
+
+
+def test_attention_bound_charges_the_q_rounding_only_where_it_happens():
+    """The fp16 rounding of a scaled Q (H max sum |q k|) is charged to the streaming kernel called with scale > 0 and to nothing
+    else: the same wrong result (two cancelling channels of Q moved one fp16 step apart) passes only where it is charged."""
+    assert la.attention_kernel(40, 128, False) == "attn2" and la.attention_kernel(40, 127, False) == "attn"
+    assert la.attention_kernel(64, 4096, True) == "attn" and la.attention_kernel(160, 4096, False) == "attn"
+    assert la.attention_kernel(512, 4096, False) == "wide"
+    assert la.attention_tile(512, 100, False) == 32 and la.attention_tile(40, 100, False) == 64
+    assert [la.attention_key_split(40, Sk, False) for Sk in (1023, 1024, 4096, 4097)] == [False, True, True, False]
+    assert not la.attention_key_split(160, 2048, False) and not la.attention_key_split(64, 2048, True)
+    assert la.attention_rounds_q(40, 330, False, 40 ** -0.5) and not la.attention_rounds_q(40, 330, False, 0.0)
+    assert not la.attention_rounds_q(40, 77, False, 40 ** -0.5) and not la.attention_rounds_q(512, 330, False, 512 ** -0.5)
+    d, Sq, Sk = 40, 8, 330
+    g = torch.Generator().manual_seed(7)
+    q = torch.zeros(Sq, d)
+    q[:, 0], q[:, 1] = 1.0, -1.0                          # two large products that cancel: the logit is the noise ...
+    k = 0.2 * torch.randn(Sk, d, generator=g)
+    k[:, :2] = 0.0
+    k[:Sk // 2, :2] = 400.0                               # ... unless the two channels of q are rounded apart
+    v = 1.0 + 0.1 * torch.randn(Sk, d, generator=g)
+    v[Sk // 2:] = 3.0
+    q, k, v = q.half(), k.half(), v.half()
+    kw = dict(tile=64, thr=ac.THR, fold=True, ones=True, pad="dup")
+    good = _attn_replay(q, k, v, **kw)
+    q_off = q.clone()
+    q_off[:, 0] = 1.0 + 2.0 ** -10                        # one fp16 step: what rounding a scaled Q channel by channel may do
+    off = _attn_replay(q_off, k, v, **kw)
+    chk = lambda got, **o: la.attention_check(got, q, k, v, 1, 1, Sq, Sk, d, scale=0.0, **o)
+    assert chk(good) <= 1.0
+    assert chk(off) > 1.0 and chk(off, q_rounded=True) <= 1.0
 
 
 # ---- ControlNet: hint stack, conv_in + hint embedding ----------------------------------------------------------------------
