@@ -387,6 +387,33 @@ int lcm_vae_posterior_renoise(const void* pre_mean, const void* pre_logvar, cons
                               const void* e0, const void* e1, float scaling_factor, float sqrt_a, float sqrt_b, void* z_out,
                               void* lat_out, void* moments_out, int B, int h, int w, int dup, void* stream);
 
+/* ---- inpainting: the mask on the device, the masked step, the overlay (csrc/inpaint.hip) ----
+ * Everything about the mask is integer arithmetic, so each result below is defined bit for bit.
+ * lcm_inpaint_mask_prepare: mask uint8 [B,H,W] (255 = repaint) -> alpha uint8 [B,H,W] and, when latmask_out != NULL, the
+ *   binary latent mask uint8 [B,H/8,W/8] (then H and W must be multiples of 8; alpha alone takes any H, W >= 1).
+ *   Blur: weights_u32 is a DEVICE array of 2 radius + 1 uint32 that sum to exactly 65536 (the caller's Gaussian, centre tap
+ *   last adjusted); t[y,x] = (sum_k w_k m[y, clamp(x + k - radius, 0, W - 1)] + 32768) >> 16 into scratch_u8 [B,H,W], then the
+ *   same down the columns of t into alpha; uint32 sums (at most 255 * 65536 + 32768).  The edge is replicated, so a radius
+ *   beyond the picture's side is fine; radius <= 80.  radius == 0: alpha = mask (a device copy, no blur launch; weights and
+ *   scratch may be NULL).  Latent mask: M = 1 where 2 * (sum of the 8 x 8 block of alpha) >= 64 * 255, else 0.
+ *   At most three launches.  Planes 8-byte aligned; B*H*W < 2^31.
+ * lcm_scheduler_step_inpaint: one LCMScheduler.step and the select, one launch.  Arguments as lcm_scheduler_step_ex, plus
+ *   z / e1 fp32 [B,4,h,w] (the init picture's clean latents and the re-noise draw) and latmask uint8 [B,h,w].  Per element
+ *   lat <- latmask ? stepped : kept, where stepped has the bits lcm_scheduler_step_ex gives for the same operands (both the
+ *   last and the non-last form) and kept = last ? z : the bits of lcm_latents_renoise(z, e1, next_sqrt_a, next_sqrt_b).
+ *   noise and e1 may be NULL when last != 0.  dup != 0: lat points at the second half of a [2B,4,h,w] state and the first
+ *   half receives the same values (as lcm_scheduler_step_handover).  eps / eps_uncond 16-byte aligned; B*4*h*w < 2^30.
+ * lcm_inpaint_composite_rgb8: rgb <- (alpha rgb + (255 - alpha) init + 127) / 255 per pixel and channel, integer division,
+ *   in place on rgb uint8 [B,H,W,3]; init uint8 [B,H,W,3], alpha uint8 [B,H,W].  alpha 255 keeps rgb, alpha 0 gives init,
+ *   exactly.  Pointers 16-byte aligned; B*H*W*3 < 2^31.
+ * Anything else is LCM_EINVAL before anything is enqueued. */
+int lcm_inpaint_mask_prepare(const void* mask_u8, const void* weights_u32, int radius, void* alpha_u8_out, void* scratch_u8,
+                             void* latmask_out, int B, int H, int W, void* stream);
+int lcm_scheduler_step_inpaint(const void* eps, const void* eps_uncond, float guidance, void* lat, const void* noise, const void* z,
+                               const void* e1, const void* latmask, const float* coef6, int last, float next_sqrt_a,
+                               float next_sqrt_b, int prediction_type, int B, int h, int w, int dup, void* stream);
+int lcm_inpaint_composite_rgb8(void* rgb_inout, const void* init_u8, const void* alpha_u8, int B, int H, int W, void* stream);
+
 /* ---- adaptive_avg_pool2d(lat,(8,8)) -> fp16 [B,4,8,8] (run_job_with_latents, backends/cuda_worker.py:299-304) */
 int lcm_latents_pool8(const void* lat, void* out_f16, int B, int h, int w, void* stream);
 

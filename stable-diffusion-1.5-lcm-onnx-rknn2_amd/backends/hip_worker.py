@@ -38,6 +38,7 @@ from .. import weights as _weights
 from . import controlnet as _controlnet
 from . import hires as _hires
 from . import img2img as _img2img
+from . import inpaint as _inpaint
 from . import refine as _refine
 
 
@@ -272,7 +273,7 @@ class _Engine:
         self.refine_cache = _refine.RefineCache(_refine.cache_bytes_from_env())
         self._stats_lock = threading.Lock()
         self.stats = dict(unet_evals=0, refine_cache_hits=0, refine_cache_misses=0, refine_cache_puts=0, controlnet_evals=0,
-                          hires_requests=0, img2img_requests=0)
+                          hires_requests=0, img2img_requests=0, inpaint_requests=0)
         # ControlNet: where it comes from (CONTROLNET=<dir or file> | "synthetic" | None); loaded on the first request that
         # carries a hint, released with the pipeline
         self.controlnet_src = None
@@ -392,6 +393,12 @@ class _Engine:
                     res = self._run_capped(items, noises, pe, kw, cap, stream, "img2img_requests", lambda idx, sub_pe, sub_noises, sub_kw:
                                            pipe.generate_img2img(sub_pe, [seeds[i] for i in idx], np.stack([items[i][3] for i in idx]),
                                                                  width, height, steps, key[7], g, noises=sub_noises, lane=lane, **sub_kw))
+                elif _inpaint.is_inpaint_key(key):   # key = plain key + (KEY_TAG, strength, mask_blur); items carry picture and mask
+                    cap = pipe.inpaint_batch_cap(width, height, steps, key[7], g, lane=lane, sizes=self.batch_sizes)
+                    res = self._run_capped(items, noises, pe, kw, cap, stream, "inpaint_requests", lambda idx, sub_pe, sub_noises, sub_kw:
+                                           pipe.generate_inpaint(sub_pe, [seeds[i] for i in idx], np.stack([items[i][3] for i in idx]),
+                                                                 np.stack([items[i][4] for i in idx]), width, height, steps, key[7],
+                                                                 key[8], g, noises=sub_noises, lane=lane, **sub_kw))
                 elif len(key) > 6 and not _controlnet.is_control_key(key):
                     res = self._run_refine(pipe, key, items, noises, pe, kw, lane, stream)
                 else:                                # plain, or ControlNet: the hints ride along, the scale is key[7]
@@ -447,7 +454,7 @@ class _Engine:
         return res
 
     def _run_capped(self, items, noises, pe, kw, cap, stream, stat, call):
-        """A hires or image-to-image batch as passes of at most ``cap`` items (the largest plan size whose split-K workspace
+        """A hires, image-to-image or inpaint batch as passes of at most ``cap`` items (the largest plan size whose split-K workspace
         need fits the lane -- the pipeline's hires_batch_cap / img2img_batch_cap: a request never fails on workspace a smaller
         pass would have served; bit-neutral, a request's bytes do not depend on its batch).  call(idx, sub_pe, sub_noises,
         sub_kw) -> the pipeline's result dict for the items ``idx``; stat: the requests counter of the kind.
@@ -725,7 +732,8 @@ class HipLcmWorker:
         refinement request (``denoise_strength`` / ``pass_number``, backends/refine.py), its strength and pass number: those
         get a key of their own (the plain fields plus (d, p)) and never share a pass with plain requests.  Hires requests
         (``enable_hr``, backends/hires.py) coalesce among themselves: the plain key + ("hires", target size, hr_steps, strength,
-        mode)."""
+        mode).  Image-to-image requests (a picture, backends/img2img.py) get the plain key + ("img2img", strength); with a mask
+        (backends/inpaint.py) they are inpaint requests with the plain key + ("inpaint", strength, mask_blur) instead."""
         width, height = parse_size(req.size)
         sl = getattr(req, "style_lora", None)
         style_id = getattr(sl, "style", None) if sl else None
@@ -737,6 +745,16 @@ class HipLcmWorker:
         ctl = _controlnet.parse_control(req)
         hr = _hires.parse_hires(req, width, height, key[2])
         i2i = _img2img.parse_img2img(req)
+        inp = _inpaint.parse_inpaint(req)            # a mask without a picture raises here
+        if inp is not None:
+            # inpaint jobs coalesce among themselves, never with image-to-image jobs: the plain key + strength and mask blur
+            if hr is not None:
+                raise RuntimeError("mask is not combined with enable_hr")
+            if rf is not None:
+                raise RuntimeError("mask is not combined with refinement (denoise_strength < 1 or pass_number > 1)")
+            if ctl is not None:
+                raise RuntimeError("mask is not combined with controlnet_image")
+            return key + (_inpaint.KEY_TAG, inp[0], inp[1])
         if i2i is not None:
             # image-to-image jobs coalesce among themselves: the plain key + the strength (the picture is per image)
             if hr is not None:
@@ -769,7 +787,7 @@ class HipLcmWorker:
         return all(v % 8 == 0 and v > 0 for v in key[:2] + more) and key[2] >= 1
 
     def _prepare(self, req, key):
-        """-> (req, seed, noise[, hint | picture]): the seed policy of cuda_worker.py:210-213 and the request's RNG stream."""
+        """-> (req, seed, noise[, hint | picture[, mask]]): the seed policy of cuda_worker.py:210-213 and the request's RNG stream."""
         eng = self._engine
         seed = int(req.seed) if getattr(req, "seed", None) is not None else int(torch.randint(0, 100_000_000, (1,)).item())
         # the request's RNG stream (initial latents, then one draw per remaining step) is drawn HERE, on the caller's
@@ -777,6 +795,12 @@ class HipLcmWorker:
         sched = eng.pipe.sched
         h8, w8, steps = key[1] // 8, key[0] // 8, key[2]
         n_draws, more = steps, ()
+        if _inpaint.is_inpaint_key(key):             # as image-to-image (the same draws), plus the fitted mask
+            eng.ensure_vae_encoder()
+            _refine.check_schedule(sched, steps, key[7])
+            _, _, pic, mask = _inpaint.parse_inpaint(req)
+            return (req, seed, draw_noise_img2img(seed, h8, w8, steps) if self._drawable(key) else None,
+                    _img2img.fit_init(pic, key[0], key[1]), _inpaint.fit_mask(mask, key[0], key[1]))
         if _img2img.is_img2img_key(key):             # encoder on first use, the schedule's own error, the picture, the draws
             eng.ensure_vae_encoder()
             _refine.check_schedule(sched, steps, key[7])
@@ -1031,6 +1055,8 @@ class HipLcmSDXLWorker(HipLcmWorker):
             raise RuntimeError("enable_hr: hires fix is not served by the SDXL worker (SD1.5 and SD 2.x only)")
         if getattr(req, "init_image", None) is not None or getattr(req, "init_images", None) is not None:
             raise RuntimeError("init_image: image-to-image is not served by the SDXL worker (SD1.5 and SD 2.x only)")
+        if getattr(req, "mask", None) is not None or getattr(req, "mask_image", None) is not None:
+            raise RuntimeError("mask: inpainting is not served by the SDXL worker (SD1.5 and SD 2.x only)")
         return HipLcmWorker._job_key(req)
 
     def _synthetic_weights(self):

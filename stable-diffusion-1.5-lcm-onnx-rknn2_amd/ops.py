@@ -535,6 +535,55 @@ def scheduler_step_handover(eps, lat, noise, xk, coef6, next_sqrt_a, next_sqrt_b
     return lat
 
 
+def _record_plain(replay):
+    """A launch with nothing to tune, in the thread's record list (``recording``): counted and replayable, never timed."""
+    RECORD = _record_list()
+    if RECORD is not None:
+        RECORD.append((None, None, replay))
+
+
+def inpaint_mask_prepare(mask_u8, weights_u32, radius, alpha_out, scratch, latmask_out, B, H, W):
+    """The inpainting mask on the device (lcm_inpaint_mask_prepare): mask uint8 [B,H,W] -> alpha uint8 [B,H,W] (the separable
+    integer blur with the DEVICE uint32 weights, 2 radius + 1 of them summing to 65536; radius 0: a copy) and the binary latent
+    mask uint8 [B,H/8,W/8] (None: alpha only).  scratch: uint8 [B,H,W], the horizontal pass's output.  -> the number of kernel
+    launches issued (0 to 3)."""
+    L = _lib.load()
+    _lib.check(L.lcm_inpaint_mask_prepare(_p(mask_u8), _p(weights_u32), int(radius), _p(alpha_out), _p(scratch), _p(latmask_out),
+                                          int(B), int(H), int(W), _stream()), "lcm_inpaint_mask_prepare")
+    launches = (2 if int(radius) > 0 else 0) + (1 if latmask_out is not None else 0)
+    for _ in range(launches):
+        _record_plain(lambda: inpaint_mask_prepare(mask_u8, weights_u32, radius, alpha_out, scratch, latmask_out, B, H, W))
+    return launches
+
+
+def scheduler_step_inpaint(eps, lat, noise, z, e1, latmask, coef6, last, next_sqrt_a, next_sqrt_b, B, h, w, *, eps_uncond=None,
+                           guidance=1.0, pred="epsilon", dup=False):
+    """One LCMScheduler.step and the inpainting select in one launch: lat <- latmask ? (the bits of ``scheduler_step``) : (z on
+    the last step, else the bits of ``latents_renoise(z, e1, next_sqrt_a, next_sqrt_b)``).  latmask uint8 [B,h,w].  dup: ``lat`` is
+    the second half of a [2B,4,h,w] state; the first half is written too."""
+    if pred not in _lib.PREDICTION_TYPES:
+        raise ValueError(f"unknown prediction type {pred!r}: expected one of {sorted(_lib.PREDICTION_TYPES)}")
+    L = _lib.load()
+    arr = (C.c_float * 6)(*[float(c) for c in coef6])
+    rc = L.lcm_scheduler_step_inpaint(_p(eps), _p(eps_uncond), float(guidance), _p(lat), _p(noise), _p(z), _p(e1), _p(latmask), arr,
+                                      int(bool(last)), float(next_sqrt_a), float(next_sqrt_b), _lib.PREDICTION_TYPES[pred],
+                                      int(B), int(h), int(w), int(bool(dup)), _stream())
+    _lib.check(rc, "lcm_scheduler_step_inpaint")
+    _record_plain(lambda: scheduler_step_inpaint(eps, lat, noise, z, e1, latmask, coef6, last, next_sqrt_a, next_sqrt_b, B, h, w,
+                                                 eps_uncond=eps_uncond, guidance=guidance, pred=pred, dup=dup))
+    return lat
+
+
+def inpaint_composite_rgb8(rgb, init_u8, alpha_u8, B, H, W):
+    """rgb <- (alpha rgb + (255 - alpha) init + 127) / 255 in integer arithmetic, in place on uint8 [B,H,W,3]
+    (lcm_inpaint_composite_rgb8); alpha uint8 [B,H,W]."""
+    L = _lib.load()
+    _lib.check(L.lcm_inpaint_composite_rgb8(_p(rgb), _p(init_u8), _p(alpha_u8), int(B), int(H), int(W), _stream()),
+               "lcm_inpaint_composite_rgb8")
+    _record_plain(lambda: inpaint_composite_rgb8(rgb, init_u8, alpha_u8, B, H, W))
+    return rgb
+
+
 def latents_pool8(lat, out, B, h, w):
     L = _lib.load()
     _lib.check(L.lcm_latents_pool8(_p(lat), _p(out), B, h, w, _stream()), "lcm_latents_pool8")

@@ -84,6 +84,24 @@ def draw_noise_img2img(seed: int, h: int, w: int, steps: int, sigma: float = 1.0
     return e0, rest
 
 
+MAX_MASK_BLUR = 32.0
+
+
+def mask_blur_weights(sigma: float):
+    """The inpainting mask's integer Gaussian (A1111's mask_blur: kernel size 2 r + 1 with r = int(2.5 sigma + 0.5)) -> (r,
+    uint32 [2 r + 1]): w_k = floor(65536 g_k / sum g) with g_k = exp(-k^2 / (2 sigma^2)) in float64, the remainder added to the
+    centre tap so that the weights sum to exactly 65536.  sigma 0 -> (0, [65536]): no blur."""
+    sigma = float(sigma)
+    r = int(2.5 * sigma + 0.5)
+    if r <= 0:
+        return 0, np.array([65536], dtype=np.uint32)
+    k = np.arange(-r, r + 1, dtype=np.float64)
+    g = np.exp(-(k * k) / (2.0 * sigma * sigma))
+    w = np.floor(65536.0 * g / g.sum()).astype(np.int64)
+    w[r] += 65536 - int(w.sum())
+    return r, w.astype(np.uint32)
+
+
 _DEFAULT_WS = {}
 
 
@@ -131,7 +149,10 @@ class _Plan:
     latents) makes it the plan of a refinement chain; None: the plain sampler (LcmHipPipeline._enqueue runs both).  The two stages of a hires request
     are plan kinds of their own: kind "latents" is the plain sampler without the VAE decode and the RGB epilogue (its result is
     P.lat), kind "from-state" a started-from-latents refinement plan whose first state the hand-over launch has already written
-    to P.lat."""
+    to P.lat.  Kind "inpaint" is a from-state plan of its own (image-to-image plans and graphs are untouched by it): it owns the
+    mask's device buffers, steps with lcm_scheduler_step_inpaint and overlays the picture after the decode."""
+
+    FROM_STATE = ("from-state", "inpaint")
 
     def __init__(self, pipe, B, h, w, steps, do_cfg, lane=None, refine=None, control=None, kind=None):
         # Every zero-fill below must be ordered before the first use on the lane's (non-blocking) stream: allocate
@@ -139,7 +160,8 @@ class _Plan:
         self.lane = lane if lane is not None else pipe.lanes[0]
         self.refine = refine
         self.control = control        # conditioning scale of a ControlNet plan (baked into the captured GEMMs); None: no hint
-        self.kind = kind              # None | "latents" | "from-state" (the stages of a hires request)
+        self.kind = kind              # None | "latents" | "from-state" (the stages of a hires request) | "inpaint"
+        self.init_img = None          # inpaint: the encoder stage's picture buffer (uint8 [B,H,W,3]), set by generate_inpaint
         with torch.cuda.stream(self.lane.stream):
             self._init(pipe, B, h, w, steps, do_cfg)
 
@@ -173,6 +195,13 @@ class _Plan:
             self.hint = torch.zeros(B, H8, W8, 3, dtype=torch.uint8, device=dev)
             self.h_hint = torch.zeros(B, H8, W8, 3, dtype=torch.uint8).pin_memory()
             self.hint_emb = torch.zeros(UB * h * w, pipe.unet.cfg["block_out_channels"][0], dtype=torch.float16, device=dev)
+        if self.kind == "inpaint":
+            H8, W8 = h * VAE_SCALE_FACTOR, w * VAE_SCALE_FACTOR
+            self.mask, self.alpha, self.mask_tmp = (torch.zeros(B, H8, W8, dtype=torch.uint8, device=dev) for _ in range(3))
+            self.latmask = torch.zeros(B, h, w, dtype=torch.uint8, device=dev)
+            self.h_mask = torch.zeros(B, H8, W8, dtype=torch.uint8).pin_memory()
+            self.h_alpha = torch.zeros(B, H8, W8, dtype=torch.uint8).pin_memory()
+            self.h_latmask = torch.zeros(B, h, w, dtype=torch.uint8).pin_memory()
         self.img_f32 = None
         self.guidance = 1.0
         self.graph = None
@@ -220,6 +249,7 @@ class LcmHipPipeline:
         self.controlnet = None
         self.vae_encoder = None                   # VAEEncoderHip, built on the first image-to-image request
         self.vae_encoder_src = None               # (host state dict with encoder.* / quant_conv.*, VAE config) or None
+        self._blur_weights = {}                   # mask_blur -> (radius, device uint32 weights) of inpaint requests
         self.lanes = [_Lane(self, 0, self.unet, self.vae)]
         self.stream = self.lanes[0].stream
         self._plans = self.lanes[0].plans
@@ -373,6 +403,93 @@ class LcmHipPipeline:
             out["moments"] = E.moments.cpu().numpy()
         return out
 
+    def _mask_weights(self, mask_blur):
+        """(radius, device uint32 weights) of a mask blur: uploaded once per value and kept (the launches bake the pointer in)."""
+        key = round(float(mask_blur), 6)
+        got = self._blur_weights.get(key)
+        if got is None:
+            with self._build_lock:
+                got = self._blur_weights.get(key)
+                if got is None:
+                    r, w = mask_blur_weights(key)
+                    got = self._blur_weights[key] = (r, torch.from_numpy(w.astype(np.int64)).to(torch.int32).to(self.device)
+                                                     if r > 0 else None)
+        return got
+
+    @torch.inference_mode()
+    def generate_inpaint(self, prompt_embeds, seeds, images_u8, masks_u8, width, height, steps, strength, mask_blur=4.0,
+                         guidance_scale=1.0, negative_embeds=None, want_float=False, noises=None, lane=0):
+        """Inpainting: ``generate_img2img`` (the same encoder stage, posterior hand-over, strength-cut schedule and RNG stream,
+        ``draw_noise_img2img``) with a mask.  masks_u8 uint8 [B,H,W] at the request's size, 255 = repaint.  On the device
+        (lcm_inpaint_mask_prepare) the mask is blurred with A1111's Gaussian of sigma ``mask_blur`` in integer arithmetic -> alpha,
+        and reduced 8 x 8 to the binary latent mask M (block mean >= 127.5).  After every scheduler step the latents outside M are
+        put back on the init picture's own noised trajectory -- z re-noised with e1 to the next timestep, z itself after the last
+        step (diffusers' StableDiffusionInpaintPipeline, 4-channel UNet) -- by lcm_scheduler_step_inpaint, which is the step
+        launch of the pass.  After the decode the uploaded picture is laid over the result per pixel:
+        out = (alpha gen + (255 - alpha) init + 127) / 255 (lcm_inpaint_composite_rgb8).  Returns generate_img2img's dict (``rgb``
+        is the overlaid picture; with want_float ``image`` is the decode before the overlay) plus ``alpha`` (host uint8 [B,H,W])
+        and ``latent_mask`` (host uint8 [B,h,w])."""
+        torch.cuda.set_device(self.device)
+        pe = torch.as_tensor(prompt_embeds)
+        B = pe.shape[0]
+        steps, strength, mask_blur = int(steps), float(strength), float(mask_blur)
+        check_size(width, height)
+        if self.unet.has_added:
+            raise LcmHipError("inpainting is not served for SDXL-family UNets")
+        if not 0.0 < strength <= 1.0:
+            raise LcmHipError(f"inpainting strength {strength} outside (0, 1]")
+        if not 0.0 <= mask_blur <= MAX_MASK_BLUR:
+            raise LcmHipError(f"mask_blur {mask_blur} outside [0, {MAX_MASK_BLUR:g}]")
+        img, msk = torch.as_tensor(images_u8), torch.as_tensor(masks_u8)
+        if img.dtype != torch.uint8 or tuple(img.shape) != (B, height, width, 3):
+            raise LcmHipError(f"init images must be uint8 [B={B}, H={height}, W={width}, 3], got {img.dtype} {tuple(img.shape)}")
+        if msk.dtype != torch.uint8 or tuple(msk.shape) != (B, height, width):
+            raise LcmHipError(f"masks must be uint8 [B={B}, H={height}, W={width}], got {msk.dtype} {tuple(msk.shape)}")
+        do_cfg = self._do_cfg(guidance_scale, negative_embeds)
+        ts = self.sched.timesteps(steps, strength)       # diffusers' error for steps > original_steps x strength, before any plan
+        nsa, nsb = self.sched.renoise_coefficients(ts[0])
+        h, w = height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR
+        P = self._from_state_plan(B, width, height, steps, strength, guidance_scale, lane, kind="inpaint")
+        L = P.lane
+        self.lane_vae_encoder(L)                         # raises for a checkpoint without an encoder, before anything is queued
+        E = self._enc_plan(L, B, height, width)
+        P.init_img = E.img                               # one buffer per (lane, B, H, W), as long-lived as the plan's graph
+        radius, wts = self._mask_weights(mask_blur)
+        for b, s in enumerate(seeds):
+            e0, rest = noises[b] if noises is not None else draw_noise_img2img(s, h, w, steps)
+            if len(rest) != steps:
+                raise LcmHipError(f"request {b}: 1 + {len(rest)} noise tensors drawn ahead, the chain needs 1 + {steps}")
+            E.h_e0[b].copy_(e0[0])
+            for i, n in enumerate(rest):
+                P.h_noise[i, b].copy_(n[0])
+        E.h_img.copy_(img)
+        P.h_mask.copy_(msk)
+
+        def upload():
+            E.img.copy_(E.h_img, non_blocking=True)
+            E.e0.copy_(E.h_e0, non_blocking=True)
+            P.mask.copy_(P.h_mask, non_blocking=True)
+
+        def front(eager):                                # encoder -> mask -> hand-over into the masked pass's state
+            pre_m, pre_l = self._encode_stage(L, E, eager)
+            enc = L.vae_enc
+            ops.inpaint_mask_prepare(P.mask, wts, radius, P.alpha, P.mask_tmp, P.latmask, B, height, width)
+            ops.vae_posterior_renoise(pre_m, pre_l, enc.w["quant.w"], enc.w["quant.b"], E.e0, P.noise[0],
+                                      self.vae.cfg["scaling_factor"], nsa, nsb, P.xk[0], P.lat, B, h, w,
+                                      moments=E.moments if want_float else None, dup=do_cfg)
+
+        def more():
+            E.h_z.copy_(P.xk[0], non_blocking=True)
+            P.h_alpha.copy_(P.alpha, non_blocking=True)
+            P.h_latmask.copy_(P.latmask, non_blocking=True)
+
+        out, _ = self._request([P], pe, negative_embeds, guidance_scale, upload, front, want_float=want_float, more=more)
+        out.update(init_latents=E.h_z.numpy().copy(), alpha=P.h_alpha.numpy().copy(), latent_mask=P.h_latmask.numpy().copy(),
+                   unet_evals=steps * (2 if do_cfg else 1))
+        if want_float:
+            out["moments"] = E.moments.cpu().numpy()
+        return out
+
     def _enqueue(self, P: _Plan, guidance: float, want_float=False, taps=None):
         """Enqueue the whole sampler on the current stream (this is what gets captured): a chain of passes, each the LCM steps
         over one schedule.  A plain plan is the one pass over timesteps(steps).  A refinement plan P.refine = (d, run, cached) is
@@ -392,7 +509,7 @@ class LcmHipPipeline:
             passes += [ts_cut] * run
         ni = 0                                        # next tensor of P.noise, in draw order
         if cached:
-            if P.kind != "from-state":                # hires stage 2: lcm_latents_upscale_renoise wrote P.lat (and P.xk[0])
+            if P.kind not in P.FROM_STATE:            # hires stage 2: lcm_latents_upscale_renoise wrote P.lat (and P.xk[0])
                 ops.latents_renoise(P.xk[0], P.noise[0], nsa, nsb, P.lat, B, h, w, dup=P.do_cfg)
             ni = 1
         elif P.do_cfg:
@@ -442,7 +559,14 @@ class LcmHipPipeline:
                 unet.forward(P.lat, int(t), kv, wemb, UB, h, w, P.eps, taps=tap1, aug=aug,
                              ta=ta_all[rows] if ta_all is not None else None, control=control)
                 coef, last = self.sched.step_coefficients(ts, i)
-                if last and j < len(passes) - 1:
+                if P.kind == "inpaint":               # the step and the select in one launch; both halves under guidance
+                    # kept cells follow the init picture: z (P.xk[0]) re-noised with e1 (P.noise[0]; the step noises follow it) to
+                    # the next timestep, z itself at the end
+                    ksa, ksb = (1.0, 0.0) if last else self.sched.renoise_coefficients(ts[i + 1])
+                    ops.scheduler_step_inpaint(eps, state, P.noise[min(ni, P.noise.shape[0] - 1)], P.xk[0], P.noise[0], P.latmask,
+                                               coef, last, ksa, ksb, B, h, w, pred=pred, dup=P.do_cfg, **kw)
+                    ni += 0 if last else 1
+                elif last and j < len(passes) - 1:
                     ops.scheduler_step_handover(eps, state, P.noise[ni], P.xk[j + 1 if cached else j], coef, nsa, nsb, B, h, w,
                                                 pred=pred, dup=P.do_cfg, **kw)
                     ni += 1
@@ -460,6 +584,8 @@ class LcmHipPipeline:
         if want_float and P.img_f32 is None:
             P.img_f32 = torch.zeros(B, h * 8, w * 8, 3, dtype=torch.float32, device=self.device)
         vae.decode(state, B, h, w, P.rgb, img_f32=P.img_f32 if want_float else None, taps=taps)
+        if P.kind == "inpaint":                       # the uploaded picture shows through where alpha < 255 (P.img_f32 stays the decode)
+            ops.inpaint_composite_rgb8(P.rgb, P.init_img, P.alpha, B, h * VAE_SCALE_FACTOR, w * VAE_SCALE_FACTOR)
         return state
 
     def plan(self, B, h, w, steps, do_cfg=False, guidance=None, lane=0, refine=None, control=None, kind=None) -> _Plan:
@@ -469,7 +595,7 @@ class LcmHipPipeline:
             key = key + (round(float(refine[0]), 6), int(refine[1]), bool(refine[2]))
         if control is not None:                      # a ControlNet plan: "control" + the conditioning scale its GEMMs bake in
             key = key + ("control", round(float(control), 6))
-        if kind is not None:                         # a stage of a hires request: "latents" (no decode) / "from-state"
+        if kind is not None:                         # a stage of a hires request: "latents" (no decode) / "from-state"; "inpaint"
             key = key + (kind,)
         L = self.lane(lane)
         P = L.plans.get(key)
@@ -596,11 +722,11 @@ class LcmHipPipeline:
             raise LcmHipError("classifier-free guidance needs negative_embeds")
         return do_cfg
 
-    def _from_state_plan(self, B, width, height, steps, strength, guidance_scale, lane) -> _Plan:
+    def _from_state_plan(self, B, width, height, steps, strength, guidance_scale, lane, kind="from-state") -> _Plan:
         """The plan of one strength-cut pass that starts from a state the hand-over launch of a front stage wrote (hires
-        stage 2, image-to-image)."""
+        stage 2, image-to-image; kind "inpaint": the masked pass of an inpaint request)."""
         return self.plan(B, height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR, int(steps), self._do_cfg(guidance_scale),
-                         guidance_scale, lane=lane, refine=(float(strength), 1, True), kind="from-state")
+                         guidance_scale, lane=lane, refine=(float(strength), 1, True), kind=kind)
 
     def _recorded_need(self, holder, L: _Lane, run) -> int:
         """_need_of one eager run() recorded on the lane's stream; remembered on ``holder`` (a plan)."""
@@ -663,6 +789,11 @@ class LcmHipPipeline:
         return self._batch_cap(width, height, steps, strength, guidance_scale, lane, sizes,
                                self.encoder_splitk_need(width, height, lane))
 
+    def inpaint_batch_cap(self, width, height, steps, strength, guidance_scale=1.0, lane=0, sizes=(1, 2, 4, 8)) -> int:
+        """img2img_batch_cap for an inpaint request: its masked pass runs the same contractions as the image-to-image pass (the
+        plan it asks is the image-to-image one) and the same encoder stage; the mask launches need no split-K workspace."""
+        return self.img2img_batch_cap(width, height, steps, strength, guidance_scale, lane, sizes)
+
     def hires_batch_cap(self, width, height, hr_steps, strength, guidance_scale=1.0, lane=0, sizes=(1, 2, 4, 8)) -> int:
         """The largest pass size of ``sizes`` whose second stage at width x height fits the lane's split-K workspace (at least
         the smallest: a batch-1 pass that does not fit raises the library's loud error when it runs)."""
@@ -694,7 +825,7 @@ class LcmHipPipeline:
                 for Q in plans:
                     self._ensure_graph(Q, guidance_scale)
             for Q in plans:
-                if Q.kind != "from-state":               # a from-state plan's first state comes from the hand-over launch
+                if Q.kind not in Q.FROM_STATE:           # a from-state plan's first state comes from the hand-over launch
                     Q.lat0.copy_(Q.h_lat, non_blocking=True)
                 Q.noise.copy_(Q.h_noise, non_blocking=True)
                 self._upload_text(Q, pe, negative_embeds, guidance_scale)
