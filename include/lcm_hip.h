@@ -414,6 +414,43 @@ int lcm_scheduler_step_inpaint(const void* eps, const void* eps_uncond, float gu
                                float next_sqrt_b, int prediction_type, int B, int h, int w, int dup, void* stream);
 int lcm_inpaint_composite_rgb8(void* rgb_inout, const void* init_u8, const void* alpha_u8, int B, int H, int W, void* stream);
 
+/* ---- ControlNet preprocessors: Canny edges and inversion (csrc/canny.hip, DESIGN.md sections 3 and 6) ----
+ * The text below DEFINES the edge picture; all of it is int32 arithmetic, so every result is defined bit for bit.  It was
+ * written to be OpenCV's cv2.Canny(rgb, low, high) on a three-channel picture with apertureSize = 3, L2gradient = False, as
+ * recalled; equality with OpenCV is UNVERIFIED (OpenCV was not available to compare against).
+ *   Input uint8 [B,H,W,3], output uint8 [B,H,W,3] with every pixel 0,0,0 or 255,255,255; B, H, W >= 1, B*H*W < 2^29.
+ *   Thresholds: lo = floor(low), hi = floor(high), swapped if lo > hi.
+ *   Gradients, per channel, borders replicated (p(y,x) with y, x clamped to the picture):
+ *     dx = (p(y-1,x+1) - p(y-1,x-1)) + 2 (p(y,x+1) - p(y,x-1)) + (p(y+1,x+1) - p(y+1,x-1))
+ *     dy = (p(y+1,x-1) - p(y-1,x-1)) + 2 (p(y+1,x) - p(y-1,x)) + (p(y+1,x+1) - p(y-1,x+1))
+ *     n = |dx| + |dy|
+ *   Channel pick: the channel with the largest n, the lowest channel index on a tie; its (dx, dy, m = n) are the pixel's.
+ *   Non-maximum suppression, with m outside the picture 0 (not replicated).  Let x = |dx|, y = |dy| << 15, t22 = x * 13573,
+ *   t67 = t22 + (x << 16).
+ *     y < t22:  peak iff m > m(y,x-1) && m >= m(y,x+1)
+ *     y > t67:  peak iff m > m(y-1,x) && m >= m(y+1,x)
+ *     else:     s = ((dx ^ dy) < 0) ? -1 : 1;  peak iff m > m(y-1,x-s) && m > m(y+1,x+s)
+ *   Class: 0 unless peak && m > lo; then 2 (strong) if m > hi, else 1 (weak).
+ *   Linking: a pixel is an edge iff its class is > 0 and its 8-connected component of class > 0 pixels holds a class-2 pixel.
+ *   Components never cross the pictures of a batch.
+ * lcm_canny_ws_bytes: the device workspace a call needs (class map, labels, marks: 16-byte padded B*H*W + 8 B*H*W bytes); 0
+ *   for a bad shape.
+ * lcm_canny_classes_u8: picture -> class map uint8 [B,H,W]; lo / hi are the integer thresholds (swapped if lo > hi).  One launch.
+ * lcm_canny_link: class map (any non-zero value other than 2 counts as weak) -> edge picture.  ws 16-byte aligned, ws_bytes >=
+ *   lcm_canny_ws_bytes; cls may be the front of ws.  Exact for every input in FOUR launches whatever the content: tile-local
+ *   union-find in LDS, a seam pass of integer atomic min over tile borders, a flatten pass that carries the strong marks to
+ *   the roots, the picture.  No workgroup waits for another and nothing is read back.  The result does not depend on the
+ *   order in which workgroups run.
+ * lcm_canny_rgb8: both stages, five launches; out_rgb may be in_rgb (in place); neither may overlap ws.
+ * lcm_invert_u8: out[i] = 255 - in[i] for n bytes (the "invert" preprocessor); in place allowed.  One launch.
+ * Nothing allocates or synchronises; the calls are capturable.  Anything else is LCM_EINVAL before anything is enqueued. */
+long long lcm_canny_ws_bytes(int B, int H, int W);
+int lcm_canny_classes_u8(const void* in_rgb, void* cls_out, int B, int H, int W, int lo, int hi, void* stream);
+int lcm_canny_link(const void* cls, void* out_rgb, void* ws, long long ws_bytes, int B, int H, int W, void* stream);
+int lcm_canny_rgb8(const void* in_rgb, void* out_rgb, void* ws, long long ws_bytes, int B, int H, int W, float low, float high,
+                   void* stream);
+int lcm_invert_u8(const void* in, void* out, long long n, void* stream);
+
 /* ---- adaptive_avg_pool2d(lat,(8,8)) -> fp16 [B,4,8,8] (run_job_with_latents, backends/cuda_worker.py:299-304) */
 int lcm_latents_pool8(const void* lat, void* out_f16, int B, int h, int w, void* stream);
 

@@ -213,6 +213,32 @@ def decode_jpeg(data) -> np.ndarray:
     return pil()
 
 
+def canny(rgb, low=100, high=200) -> np.ndarray:
+    """uint8 [H,W,3] (or [B,H,W,3]) host pixels -> the Canny edge picture of the same shape, every pixel 0,0,0 or 255,255,255,
+    as include/lcm_hip.h defines it (written after ``cv2.Canny(rgb, low, high)``; equality with OpenCV is unverified): the
+    pixels are uploaded to the current device, ``lcm_canny_rgb8`` (csrc/canny.hip) runs there and the map is read back.  A
+    request that wants the map as its ControlNet hint sends the photo with ``controlnet_module="canny"`` instead and nothing
+    comes back to the host.  No CPU fallback."""
+    from .. import ops as _ops
+    a = np.ascontiguousarray(rgb)
+    if a.dtype != np.uint8 or a.ndim not in (3, 4) or a.shape[-1] != 3 or min(a.shape) < 1:
+        raise ValueError(f"canny expects uint8 [H][W][3] or [B][H][W][3], got {a.dtype} {tuple(a.shape)}")
+    low, high = float(low), float(high)
+    if not (abs(low) < 1e9 and abs(high) < 1e9):
+        raise ValueError(f"canny thresholds must be finite numbers, got {low!r}, {high!r}")
+    if not torch.cuda.is_available():
+        raise LcmHipError("canny needs an MI355X; no CPU fallback exists on this path")
+    B, H, W = (1,) + a.shape[:2] if a.ndim == 3 else a.shape[:3]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stream = torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(stream):
+        src = torch.from_numpy(a.reshape(B, H, W, 3)).to(dev)
+        ws = torch.empty(_ops.canny_ws_bytes(B, H, W), dtype=torch.uint8, device=dev)
+        _ops.canny_rgb8(src, src, ws, B, H, W, low, high)
+        host = src.cpu()
+    return host.numpy().reshape(a.shape)
+
+
 def _rows(x, idx, n):
     """The per-request conditioning rows ``idx`` of a batch of n: tensors with n leading rows are gathered, tuples (SDXL's
     ``added``) and dicts walked, anything else passed through; the whole batch in order is returned as it is."""
@@ -273,7 +299,7 @@ class _Engine:
         self.refine_cache = _refine.RefineCache(_refine.cache_bytes_from_env())
         self._stats_lock = threading.Lock()
         self.stats = dict(unet_evals=0, refine_cache_hits=0, refine_cache_misses=0, refine_cache_puts=0, controlnet_evals=0,
-                          hires_requests=0, img2img_requests=0, inpaint_requests=0)
+                          hires_requests=0, img2img_requests=0, inpaint_requests=0, controlnet_preprocessed=0)
         # ControlNet: where it comes from (CONTROLNET=<dir or file> | "synthetic" | None); loaded on the first request that
         # carries a hint, released with the pipeline
         self.controlnet_src = None
@@ -403,13 +429,17 @@ class _Engine:
                     res = self._run_refine(pipe, key, items, noises, pe, kw, lane, stream)
                 else:                                # plain, or ControlNet: the hints ride along, the scale is key[7]
                     control = _controlnet.is_control_key(key)
+                    pre = _controlnet.key_preprocessor(key) if control else ()
                     if control:
                         kw = dict(kw, control=(np.stack([it[3] for it in items]), key[7]))
+                        if pre:                          # a photo: the edge map is made on the device, ahead of the hint stack
+                            kw["preprocess"] = pre
                     out = pipe.generate(pe, seeds, width, height, steps, g, noises=noises, lane=lane, **kw)
                     res = _take([None] * len(items), out, range(len(items)))
                     with self._stats_lock:
                         self.stats["unet_evals"] += steps
                         self.stats["controlnet_evals"] += steps if control else 0
+                        self.stats["controlnet_preprocessed"] += len(items) if pre else 0
             finally:
                 self._leave_style()
         t2 = _t.perf_counter()
@@ -771,10 +801,11 @@ class HipLcmWorker:
                 raise RuntimeError("enable_hr is not combined with controlnet_image")
             return key + (_hires.KEY_TAG,) + hr
         if ctl is not None:
-            # ControlNet jobs coalesce among themselves: the plain key + the conditioning scale (the hint is per image)
+            # ControlNet jobs coalesce among themselves: the plain key + the conditioning scale (the hint is per image) and,
+            # with a preprocessor, its name and parameters: ("canny", lo, hi) / ("invert",)
             if rf is not None:
                 raise RuntimeError("controlnet_image is not combined with refinement (denoise_strength < 1 or pass_number > 1)")
-            return key + (_controlnet.KEY_TAG, ctl[0])
+            return key + (_controlnet.KEY_TAG, ctl[0]) + _controlnet.parse_preprocessor(req)
         return key if rf is None else key + rf
 
     def _run_batch(self, key, items):

@@ -66,6 +66,10 @@ _SIGS = {
     "lcm_inpaint_mask_prepare": [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp],
     "lcm_scheduler_step_inpaint": [_vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_float), _i, _f, _f, _i, _i, _i, _i, _i, _vp],
     "lcm_inpaint_composite_rgb8": [_vp, _vp, _vp, _i, _i, _i, _vp],
+    "lcm_canny_classes_u8": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "lcm_canny_link": [_vp, _vp, _vp, C.c_longlong, _i, _i, _i, _vp],
+    "lcm_canny_rgb8": [_vp, _vp, _vp, C.c_longlong, _i, _i, _i, _f, _f, _vp],
+    "lcm_invert_u8": [_vp, _vp, C.c_longlong, _vp],
     "lcm_png_encode_rgb8": [_vp, _i, _i, C.c_longlong, _i, _vp, C.c_longlong, C.POINTER(C.c_longlong)],
     "lcm_stream_create": [C.POINTER(_vp)],
     "lcm_stream_destroy": [_vp],
@@ -116,7 +120,7 @@ _SIGS = {
     "lcm_jpeg_idct_rgb8": [_vp, C.c_longlong, _vp, _vp, C.c_longlong, _vp, C.c_longlong, _vp],
 }
 EXPORTS = tuple(sorted(list(_SIGS) + ["lcm_last_error", "lcm_version", "lcm_groupnorm_ws_bytes", "lcm_stats_bytes", "lcm_png_bound",
-                              "lcm_jpeg_coef_bytes", "lcm_jpeg_bound"]))
+                              "lcm_canny_ws_bytes", "lcm_jpeg_coef_bytes", "lcm_jpeg_bound"]))
 
 EUNSUPPORTED = -3          # LCM_EUNSUPPORTED: a well-formed input the library leaves to another decoder
 
@@ -156,6 +160,8 @@ def load():
     lib.lcm_png_bound.restype = C.c_longlong
     lib.lcm_png_bound.argtypes = [_i, _i, _i]
     lib.lcm_stats_bytes.argtypes = [_i, _i, _i]
+    lib.lcm_canny_ws_bytes.restype = C.c_longlong
+    lib.lcm_canny_ws_bytes.argtypes = [_i, _i, _i]
     for fn in (lib.lcm_jpeg_coef_bytes, lib.lcm_jpeg_bound):
         fn.restype = C.c_longlong
         fn.argtypes = [_i, _i]

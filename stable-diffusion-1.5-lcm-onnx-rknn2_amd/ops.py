@@ -584,6 +584,43 @@ def inpaint_composite_rgb8(rgb, init_u8, alpha_u8, B, H, W):
     return rgb
 
 
+def canny_ws_bytes(B, H, W):
+    """Bytes of device workspace a Canny call on uint8 [B,H,W,3] needs (lcm_canny_ws_bytes)."""
+    return int(_lib.load().lcm_canny_ws_bytes(int(B), int(H), int(W)))
+
+
+def canny_classes(rgb_u8, cls_out, B, H, W, lo, hi):
+    """Picture uint8 [B,H,W,3] -> class map uint8 [B,H,W] (0 nothing, 1 weak, 2 strong) for the integer thresholds lo, hi."""
+    L = _lib.load()
+    _lib.check(L.lcm_canny_classes_u8(_p(rgb_u8), _p(cls_out), int(B), int(H), int(W), int(lo), int(hi), _stream()),
+               "lcm_canny_classes_u8")
+    return cls_out
+
+
+def canny_link(cls_u8, out_rgb, ws, B, H, W):
+    """Class map uint8 [B,H,W] -> edge picture uint8 [B,H,W,3] (hysteresis; lcm_canny_link).  ws: uint8 device workspace of at
+    least ``canny_ws_bytes`` bytes."""
+    L = _lib.load()
+    _lib.check(L.lcm_canny_link(_p(cls_u8), _p(out_rgb), _p(ws), int(ws.numel() * ws.element_size()), int(B), int(H), int(W),
+                                _stream()), "lcm_canny_link")
+    return out_rgb
+
+
+def canny_rgb8(rgb_u8, out_rgb, ws, B, H, W, low=100.0, high=200.0):
+    """The Canny edge picture of uint8 [B,H,W,3] into out_rgb (may be rgb_u8), as include/lcm_hip.h defines it."""
+    L = _lib.load()
+    _lib.check(L.lcm_canny_rgb8(_p(rgb_u8), _p(out_rgb), _p(ws), int(ws.numel() * ws.element_size()), int(B), int(H), int(W),
+                                float(low), float(high), _stream()), "lcm_canny_rgb8")
+    return out_rgb
+
+
+def invert_u8(x, out):
+    """out = 255 - x over uint8 tensors of one size (lcm_invert_u8); out may be x."""
+    L = _lib.load()
+    _lib.check(L.lcm_invert_u8(_p(x), _p(out), int(x.numel()), _stream()), "lcm_invert_u8")
+    return out
+
+
 def latents_pool8(lat, out, B, h, w):
     L = _lib.load()
     _lib.check(L.lcm_latents_pool8(_p(lat), _p(out), B, h, w, _stream()), "lcm_latents_pool8")

@@ -141,6 +141,7 @@ class _Lane:
         self.controlnet = None        # this lane's executor of the pipeline's ControlNet (LcmHipPipeline.lane_controlnet)
         self._controlnet_of = None
         self.vae_enc = None           # this lane's executor of the VAE encoder (LcmHipPipeline.lane_vae_encoder)
+        self.pre_ws = None            # ControlNet preprocessor (generate(preprocess=)): the Canny workspace, sized on first use
         self.enc_plans = {}           # (B, H, W) -> _EncPlan: the encoder stage of image-to-image requests
 
 
@@ -902,7 +903,7 @@ class LcmHipPipeline:
     @torch.inference_mode()
     def generate(self, prompt_embeds, seeds, width, height, steps, guidance_scale=1.0, negative_embeds=None,
                  want_float=False, taps=None, latents=None, added=None, negative_added=None, noises=None, lane=0,
-                 strength=None, passes=0, start=None, control=None, hires=None):
+                 strength=None, passes=0, start=None, control=None, hires=None, preprocess=None):
         """prompt_embeds: [B,77,ctx] (any float dtype, host or device); seeds: B ints.  noises: optional per-request
         ``draw_noise(seed, h, w, steps - 1, init_noise_sigma)`` results drawn ahead by the callers (the worker's pool
         threads draw them in parallel, off the dispatcher's serial path); None: drawn here from the seeds.
@@ -919,6 +920,10 @@ class LcmHipPipeline:
         ControlNet of set_controlnet.  The scale is part of the plan key (the captured GEMMs carry it as a scalar argument);
         the hint is uploaded per request into the plan's fixed buffer.  Not combined with passes.  The result then carries
         ``controlnet_evals``.
+        preprocess = ("canny", low, high) | ("invert",): the hint is a photo, and its edge map (include/lcm_hip.h, Canny) or its
+        inverse is computed on the lane's stream, between the upload and the captured pass, into the buffer the hint stack reads
+        (csrc/canny.hip; per-lane workspace sized on first use).  It is no part of the plan key: plans, graphs and launches of
+        the pass are those of a finished hint.  None / (): the hint is the finished map.  Needs control.
         hires = (W2, H2, hr_steps, strength, mode): hires fix -- ``generate_hires`` (its own RNG contract and result keys); not
         combined with passes, control, latents or SDXL conditioning.
         Returns dict(rgb uint8 [B,H,W,3] (host), latents fp32 [B,4,h,w] (host), pool8 fp16 [B,4,8,8] (host))."""
@@ -969,6 +974,12 @@ class LcmHipPipeline:
             hint = torch.as_tensor(hint)
             if hint.dtype != torch.uint8 or tuple(hint.shape) != (B, height, width, 3):
                 raise LcmHipError(f"ControlNet hint must be uint8 [B={B}, H={height}, W={width}, 3], got {hint.dtype} {tuple(hint.shape)}")
+        pre = tuple(preprocess) if preprocess else ()
+        if pre:
+            if control is None:
+                raise LcmHipError("a ControlNet preprocessor needs a hint to work on (control=)")
+            if not ((pre[0] == "canny" and len(pre) == 3) or pre == ("invert",)):
+                raise LcmHipError(f"unknown ControlNet preprocessor {pre!r}: expected ('canny', low, high) or ('invert',)")
         P = self.plan(B, h, w, steps, do_cfg, guidance_scale, lane=lane, refine=refine, control=cscale)
         with torch.cuda.stream(P.lane.stream):       # latents= and the hint may be device tensors
             for b, s in enumerate(seeds):
@@ -988,7 +999,9 @@ class LcmHipPipeline:
                 P.h_hint.copy_(hint)
 
         def upload():
-            if hint is not None:
+            if hint is not None and pre:
+                self._preprocess_hint(P, pre, B, height, width)
+            elif hint is not None:
                 P.hint.copy_(P.h_hint, non_blocking=True)
             if refine is not None and refine[2]:
                 for b in range(B):
@@ -1004,6 +1017,19 @@ class LcmHipPipeline:
         if control is not None:
             out["controlnet_evals"] = steps
         return out
+
+    def _preprocess_hint(self, P: _Plan, pre, B, H, W):
+        """The photo in P.h_hint -> the map in P.hint, on the current (the lane's) stream: the usual upload, then the preprocessor's
+        launches in place (the picture is read by the first launch only, the map written by the last).  Nothing is read back."""
+        P.hint.copy_(P.h_hint, non_blocking=True)
+        if pre[0] == "invert":
+            ops.invert_u8(P.hint, P.hint)
+            return
+        L = P.lane
+        need = ops.canny_ws_bytes(B, H, W)
+        if L.pre_ws is None or L.pre_ws.numel() < need:
+            L.pre_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ops.canny_rgb8(P.hint, P.hint, L.pre_ws, B, H, W, float(pre[1]), float(pre[2]))
 
     # hot loop only (device resident inputs already in the plan): used by bench.py
     def replay(self, P: _Plan):
