@@ -451,6 +451,54 @@ int lcm_canny_rgb8(const void* in_rgb, void* out_rgb, void* ws, long long ws_byt
                    void* stream);
 int lcm_invert_u8(const void* in, void* out, long long n, void* stream);
 
+/* ---- Lanczos resampler: fitting an upload to the request's size (csrc/resize.hip, csrc/resize.cpp) ----
+ * The text below DEFINES the fitted picture bit for bit.  It is PIL's ImagingResample for 8-bit pixels with the Lanczos filter:
+ * Image.resize((out_w, out_h), Image.LANCZOS) of an "L" or "RGB" picture gives the same bytes (verified against Pillow 12.2.0 by
+ * tests/test_resize_cpu.py and tests/test_resize_gpu.py; other Pillow versions are unverified).
+ *   Tables, per axis with source size `in` and output size `out`, in IEEE double on the host, no fused or reordered operation:
+ *     scale = in / out;  fs = max(scale, 1.0);  support = 3.0 * fs;  ksize = (int)ceil(support) * 2 + 1;  ss = 1.0 / fs
+ *     for output xx:  center = (xx + 0.5) * scale
+ *       xmin = max(0, (int)(center - support + 0.5));  xmax = min(in, (int)(center + support + 0.5));  n = xmax - xmin
+ *       w[x] = L((x + xmin - center + 0.5) * ss) for x < n;  ww = the sum of w in index order;  w[x] /= ww if ww != 0
+ *     L(x) = sinc(x) * sinc(x / 3) for -3 <= x < 3, else 0;  sinc(0) = 1, otherwise sinc(x) = sin(pi x) / (pi x), libm's sin
+ *     k[x] = (int)(w[x] * 2^22 + 0.5) for w[x] >= 0, (int)(w[x] * 2^22 - 0.5) otherwise (truncation towards zero)
+ *   One pass along an axis:  acc = 2^21 + sum_{x<n} pix[xmin + x] * k[x]  in int32 (|acc| < 2^31 always);
+ *     out = clamp(acc >> 22, 0, 255), arithmetic shift.
+ *   Order: the horizontal pass first, into a uint8 intermediate (rounded and clipped), then the vertical pass over it.  A pass
+ *   whose axis keeps its size does not run (PIL skips it too; its table would be the identity).  Only the source rows the
+ *   vertical tables read are resampled horizontally.
+ *   Window: a call computes the w x h pixels at (x0, y0) of the full out_w x out_h grid and nothing else.  A window position
+ *   outside the grid takes the nearest grid position on that axis (edge replication: the bands of "resize and fill").
+ *   Domain: C = 1 or 3 interleaved channels; source sides 1..8192; output and window sides 1..4096; x0, y0 in -4096..4096.
+ *   (Image.resize runs the vertical pass FIRST for height > 100 * width && out_h < height: callers that want PIL's bytes keep
+ *   such pictures away from this path -- backends/hip_worker.resize does.)
+ * Host-only, no device needed:
+ *   lcm_resize_ksize: ksize of an axis;  lcm_resize_table_bytes: bytes of the table of n outputs of an axis, 16-byte padded:
+ *     int32 [n][2] (xmin, taps), then int32 [n][ksize] coefficients, zero behind the taps;  0 for a bad axis.
+ *   lcm_resize_tables: that table for outputs o0 .. o0 + n - 1 (each clamped to the grid) into host memory.
+ *   lcm_resize_span: the source range [first, last) those outputs read;  lcm_resize_max_span: the most source pixels that `tile`
+ *     neighbouring outputs read together.
+ *   lcm_resize_passes: bit 0 the horizontal pass runs, bit 1 the vertical one (both sizes kept: the horizontal pass copies).
+ *   lcm_resize_plan_table_bytes / lcm_resize_plan_tables: the tables of a whole call -- the horizontal pass's, then the vertical
+ *     pass's, each only if it runs -- as the head of the workspace holds them.
+ * lcm_resize_ws_bytes: the device workspace of a call: those tables, then the intermediate (16-byte padded); 0 for bad geometry.
+ * lcm_resize_lanczos_u8: src uint8 [sh][sw][C] with row stride src_stride bytes -> the window into dst, rows dst_stride bytes
+ *   apart (so a slot of a batch tensor is written in place).  The CALLER has put lcm_resize_plan_tables' bytes at the front of
+ *   ws (16-byte aligned) on the same stream before the call.  At most one launch per pass; rows need no alignment; no
+ *   workgroup waits for another; nothing allocates, synchronises or is read back; capturable.  src, dst and ws must not
+ *   overlap.  Anything else is LCM_EINVAL before anything is enqueued. */
+int lcm_resize_ksize(int in, int out);
+long long lcm_resize_table_bytes(int in, int out, int n);
+int lcm_resize_tables(int in, int out, int o0, int n, void* host_dst, long long dst_bytes);
+int lcm_resize_span(int in, int out, int o0, int n, int* first, int* last);
+int lcm_resize_max_span(int in, int out, int o0, int n, int tile);
+int lcm_resize_passes(int sw, int sh, int out_w, int out_h);
+long long lcm_resize_plan_table_bytes(int sw, int sh, int out_w, int out_h, int w, int h);
+int lcm_resize_plan_tables(int sw, int sh, int out_w, int out_h, int x0, int y0, int w, int h, void* host_dst, long long dst_bytes);
+long long lcm_resize_ws_bytes(int C, int sw, int sh, int out_w, int out_h, int x0, int y0, int w, int h);
+int lcm_resize_lanczos_u8(const void* src, long long src_stride, int C, int sw, int sh, int out_w, int out_h, int x0, int y0, int w,
+                          int h, void* dst, long long dst_stride, void* ws, long long ws_bytes, void* stream);
+
 /* ---- adaptive_avg_pool2d(lat,(8,8)) -> fp16 [B,4,8,8] (run_job_with_latents, backends/cuda_worker.py:299-304) */
 int lcm_latents_pool8(const void* lat, void* out_f16, int B, int h, int w, void* stream);
 

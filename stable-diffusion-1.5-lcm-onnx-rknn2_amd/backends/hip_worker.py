@@ -14,6 +14,8 @@ Env (as the reference, backends/cuda_worker.py:43-61):
   CUDA_DEVICE / HIP_DEVICE   default cuda:0 (torch's name for the HIP device)
   LCM_REFINE_CACHE_MB        device-resident cache of refinement latents (denoise_strength / pass_number requests), MB per
                              engine; default 64, 0 turns it off
+  LCM_RESIZE                 hip (default) | pil: where an upload of another size than the request's is fitted -- the HIP Lanczos
+                             resampler on the lane's stream, or PIL on the caller's thread; the bytes are the same (backends/fit.py)
   CUDA_DTYPE                 fp16 (default).  bf16 / fp32 -- which the reference honours -- are REFUSED unless LCM_HIP_DTYPE=fp16
                              says to run them in this backend's one arithmetic (fp16 operands, fp32 accumulation)
 """
@@ -36,6 +38,7 @@ from ..prompt import HipPromptEncoder
 from ..scheduler import LCMSchedule
 from .. import weights as _weights
 from . import controlnet as _controlnet
+from . import fit as _fit
 from . import hires as _hires
 from . import img2img as _img2img
 from . import inpaint as _inpaint
@@ -239,6 +242,40 @@ def canny(rgb, low=100, high=200) -> np.ndarray:
     return host.numpy().reshape(a.shape)
 
 
+def resize(img, width, height, mode=0) -> np.ndarray:
+    """uint8 [H,W] or [H,W,3] host pixels -> the picture fitted to width x height under ``resize_mode`` ``mode`` (0 just resize,
+    1 crop and resize, 2 resize and fill; backends/fit.py), with the bytes of PIL's ``Image.resize(..., Image.LANCZOS)``: the
+    pixels are uploaded to the current device, ``lcm_resize_lanczos_u8`` (csrc/resize.hip) computes the request's window there
+    and it is read back.  A picture that already has the size comes back as it is.  Pictures outside the device path's domain
+    (``fit.in_domain``: sides above 8192 / 4096, taller than 100 x their width) and everything under LCM_RESIZE=pil go to PIL.
+    A request that carries its upload at another size needs no call: the worker fits it on its lane's stream."""
+    from .. import ops as _ops
+    a = np.ascontiguousarray(img)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3) or min(a.shape) < 1:
+        raise ValueError(f"resize expects uint8 [H][W] or [H][W][3], got {a.dtype} {tuple(a.shape)}")
+    width, height, mode = int(width), int(height), int(mode)
+    if mode not in _fit.MODES:
+        raise ValueError(f"resize mode {mode!r}: expected one of {sorted(_fit.MODES)}")
+    if width < 1 or height < 1:
+        raise ValueError(f"resize to {width}x{height}")
+    f = _fit.prepare(a, width, height, mode)
+    if not _fit.is_pending(f):
+        return f
+    if not torch.cuda.is_available():
+        raise LcmHipError("resize needs an MI355X on this path (LCM_RESIZE=pil uses PIL)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stream = torch.cuda.current_stream(dev)
+    win = (f.x0, f.y0, width, height)
+    with torch.cuda.device(dev), torch.cuda.stream(stream):
+        src = torch.from_numpy(a).to(dev)
+        dst = torch.empty(f.shape, dtype=torch.uint8, device=dev)
+        ws = torch.empty(_ops.resize_ws_bytes(a.shape[1], a.shape[0], 1 if a.ndim == 2 else 3, f.fit_w, f.fit_h, win),
+                         dtype=torch.uint8, device=dev)
+        _ops.resize_lanczos_u8(src, dst, ws, f.fit_w, f.fit_h, win)
+        host = dst.cpu()
+    return host.numpy()
+
+
 def _rows(x, idx, n):
     """The per-request conditioning rows ``idx`` of a batch of n: tensors with n leading rows are gathered, tuples (SDXL's
     ``added``) and dicts walked, anything else passed through; the whole batch in order is returned as it is."""
@@ -299,7 +336,8 @@ class _Engine:
         self.refine_cache = _refine.RefineCache(_refine.cache_bytes_from_env())
         self._stats_lock = threading.Lock()
         self.stats = dict(unet_evals=0, refine_cache_hits=0, refine_cache_misses=0, refine_cache_puts=0, controlnet_evals=0,
-                          hires_requests=0, img2img_requests=0, inpaint_requests=0, controlnet_preprocessed=0)
+                          hires_requests=0, img2img_requests=0, inpaint_requests=0, controlnet_preprocessed=0,
+                          resized_on_device=0)
         # ControlNet: where it comes from (CONTROLNET=<dir or file> | "synthetic" | None); loaded on the first request that
         # carries a hint, released with the pipeline
         self.controlnet_src = None
@@ -417,13 +455,13 @@ class _Engine:
                 elif _img2img.is_img2img_key(key):   # key = plain key + (KEY_TAG, strength); items carry the fitted picture
                     cap = pipe.img2img_batch_cap(width, height, steps, key[7], g, lane=lane, sizes=self.batch_sizes)
                     res = self._run_capped(items, noises, pe, kw, cap, stream, "img2img_requests", lambda idx, sub_pe, sub_noises, sub_kw:
-                                           pipe.generate_img2img(sub_pe, [seeds[i] for i in idx], np.stack([items[i][3] for i in idx]),
+                                           pipe.generate_img2img(sub_pe, [seeds[i] for i in idx], _fit.stack([items[i][3] for i in idx]),
                                                                  width, height, steps, key[7], g, noises=sub_noises, lane=lane, **sub_kw))
                 elif _inpaint.is_inpaint_key(key):   # key = plain key + (KEY_TAG, strength, mask_blur); items carry picture and mask
                     cap = pipe.inpaint_batch_cap(width, height, steps, key[7], g, lane=lane, sizes=self.batch_sizes)
                     res = self._run_capped(items, noises, pe, kw, cap, stream, "inpaint_requests", lambda idx, sub_pe, sub_noises, sub_kw:
-                                           pipe.generate_inpaint(sub_pe, [seeds[i] for i in idx], np.stack([items[i][3] for i in idx]),
-                                                                 np.stack([items[i][4] for i in idx]), width, height, steps, key[7],
+                                           pipe.generate_inpaint(sub_pe, [seeds[i] for i in idx], _fit.stack([items[i][3] for i in idx]),
+                                                                 _fit.stack([items[i][4] for i in idx]), width, height, steps, key[7],
                                                                  key[8], g, noises=sub_noises, lane=lane, **sub_kw))
                 elif len(key) > 6 and not _controlnet.is_control_key(key):
                     res = self._run_refine(pipe, key, items, noises, pe, kw, lane, stream)
@@ -431,7 +469,7 @@ class _Engine:
                     control = _controlnet.is_control_key(key)
                     pre = _controlnet.key_preprocessor(key) if control else ()
                     if control:
-                        kw = dict(kw, control=(np.stack([it[3] for it in items]), key[7]))
+                        kw = dict(kw, control=(_fit.stack([it[3] for it in items]), key[7]))
                         if pre:                          # a photo: the edge map is made on the device, ahead of the hint stack
                             kw["preprocess"] = pre
                     out = pipe.generate(pe, seeds, width, height, steps, g, noises=noises, lane=lane, **kw)
@@ -440,6 +478,12 @@ class _Engine:
                         self.stats["unet_evals"] += steps
                         self.stats["controlnet_evals"] += steps if control else 0
                         self.stats["controlnet_preprocessed"] += len(items) if pre else 0
+                # requests of this batch with an upload that the device fitted (LCM_RESIZE=hip): the pipeline's upload() ran the
+                # resampler into their slots
+                fitted = len({id(it) for it in items if any(_fit.is_pending(x) for x in it[3:])})
+                if fitted:
+                    with self._stats_lock:
+                        self.stats["resized_on_device"] += fitted
             finally:
                 self._leave_style()
         t2 = _t.perf_counter()
@@ -776,6 +820,8 @@ class HipLcmWorker:
         hr = _hires.parse_hires(req, width, height, key[2])
         i2i = _img2img.parse_img2img(req)
         inp = _inpaint.parse_inpaint(req)            # a mask without a picture raises here
+        if i2i is not None:
+            _fit.parse_resize_mode(req)              # its own error, for its own job; no part of the key (the picture is per image)
         if inp is not None:
             # inpaint jobs coalesce among themselves, never with image-to-image jobs: the plain key + strength and mask blur
             if hr is not None:
@@ -818,7 +864,9 @@ class HipLcmWorker:
         return all(v % 8 == 0 and v > 0 for v in key[:2] + more) and key[2] >= 1
 
     def _prepare(self, req, key):
-        """-> (req, seed, noise[, hint | picture[, mask]]): the seed policy of cuda_worker.py:210-213 and the request's RNG stream."""
+        """-> (req, seed, noise[, hint | picture[, mask]]): the seed policy of cuda_worker.py:210-213 and the request's RNG stream.
+        An upload that does not have the request's size is fitted here on the host (LCM_RESIZE=pil, or outside the device path's
+        domain) or handed on at its own size as a ``fit.Pending`` for the lane's stream to fit (backends/fit.py)."""
         eng = self._engine
         seed = int(req.seed) if getattr(req, "seed", None) is not None else int(torch.randint(0, 100_000_000, (1,)).item())
         # the request's RNG stream (initial latents, then one draw per remaining step) is drawn HERE, on the caller's
@@ -830,12 +878,13 @@ class HipLcmWorker:
             eng.ensure_vae_encoder()
             _refine.check_schedule(sched, steps, key[7])
             _, _, pic, mask = _inpaint.parse_inpaint(req)
+            mode = _fit.parse_resize_mode(req)       # picture and mask alike, as in A1111
             return (req, seed, draw_noise_img2img(seed, h8, w8, steps) if self._drawable(key) else None,
-                    _img2img.fit_init(pic, key[0], key[1]), _inpaint.fit_mask(mask, key[0], key[1]))
+                    _fit.prepare(pic, key[0], key[1], mode, _img2img.fit_init), _fit.prepare(mask, key[0], key[1], mode, _inpaint.fit_mask))
         if _img2img.is_img2img_key(key):             # encoder on first use, the schedule's own error, the picture, the draws
             eng.ensure_vae_encoder()
             _refine.check_schedule(sched, steps, key[7])
-            pic = _img2img.fit_init(_img2img.parse_img2img(req)[1], key[0], key[1])
+            pic = _fit.prepare(_img2img.parse_img2img(req)[1], key[0], key[1], _fit.parse_resize_mode(req), _img2img.fit_init)
             return (req, seed, draw_noise_img2img(seed, h8, w8, steps) if self._drawable(key) else None, pic)
         if _hires.is_hires_key(key):                 # the schedule's own error first, then the draws at both shapes
             tw, th, hr_steps, strength = key[7:11]
@@ -844,7 +893,7 @@ class HipLcmWorker:
                     if self._drawable(key, tw, th) else None)
         if _controlnet.is_control_key(key):
             eng.ensure_controlnet()                  # lazily, on the caller's thread; raises for this job
-            more = (_controlnet.fit_hint(_controlnet.parse_control(req)[1], key[0], key[1]),)
+            more = (_fit.prepare(_controlnet.parse_control(req)[1], key[0], key[1], _fit.JUST_RESIZE, _controlnet.fit_hint),)
         elif len(key) > 6:                           # refinement: the schedule's own error first, then the whole chain's draws
             _refine.check_schedule(sched, steps, key[6])
             n_draws = _refine.noise_draws(steps, key[7])

@@ -70,6 +70,13 @@ _SIGS = {
     "lcm_canny_link": [_vp, _vp, _vp, C.c_longlong, _i, _i, _i, _vp],
     "lcm_canny_rgb8": [_vp, _vp, _vp, C.c_longlong, _i, _i, _i, _f, _f, _vp],
     "lcm_invert_u8": [_vp, _vp, C.c_longlong, _vp],
+    "lcm_resize_lanczos_u8": [_vp, C.c_longlong, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_longlong, _vp, C.c_longlong, _vp],
+    "lcm_resize_tables": [_i, _i, _i, _i, _vp, C.c_longlong],
+    "lcm_resize_plan_tables": [_i] * 8 + [_vp, C.c_longlong],
+    "lcm_resize_span": [_i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i)],
+    "lcm_resize_ksize": [_i, _i],
+    "lcm_resize_passes": [_i, _i, _i, _i],
+    "lcm_resize_max_span": [_i, _i, _i, _i, _i],
     "lcm_png_encode_rgb8": [_vp, _i, _i, C.c_longlong, _i, _vp, C.c_longlong, C.POINTER(C.c_longlong)],
     "lcm_stream_create": [C.POINTER(_vp)],
     "lcm_stream_destroy": [_vp],
@@ -120,7 +127,8 @@ _SIGS = {
     "lcm_jpeg_idct_rgb8": [_vp, C.c_longlong, _vp, _vp, C.c_longlong, _vp, C.c_longlong, _vp],
 }
 EXPORTS = tuple(sorted(list(_SIGS) + ["lcm_last_error", "lcm_version", "lcm_groupnorm_ws_bytes", "lcm_stats_bytes", "lcm_png_bound",
-                              "lcm_canny_ws_bytes", "lcm_jpeg_coef_bytes", "lcm_jpeg_bound"]))
+                              "lcm_canny_ws_bytes", "lcm_jpeg_coef_bytes", "lcm_jpeg_bound", "lcm_resize_ws_bytes",
+                              "lcm_resize_table_bytes", "lcm_resize_plan_table_bytes"]))
 
 EUNSUPPORTED = -3          # LCM_EUNSUPPORTED: a well-formed input the library leaves to another decoder
 
@@ -162,6 +170,9 @@ def load():
     lib.lcm_stats_bytes.argtypes = [_i, _i, _i]
     lib.lcm_canny_ws_bytes.restype = C.c_longlong
     lib.lcm_canny_ws_bytes.argtypes = [_i, _i, _i]
+    for fn, n in ((lib.lcm_resize_ws_bytes, 9), (lib.lcm_resize_table_bytes, 3), (lib.lcm_resize_plan_table_bytes, 6)):
+        fn.restype = C.c_longlong
+        fn.argtypes = [_i] * n
     for fn in (lib.lcm_jpeg_coef_bytes, lib.lcm_jpeg_bound):
         fn.restype = C.c_longlong
         fn.argtypes = [_i, _i]

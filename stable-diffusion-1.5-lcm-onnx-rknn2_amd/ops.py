@@ -25,6 +25,7 @@ def _stream():
 #   profiling():  every such launch appends the record of its algorithmic work (bench.py's roofline leg pairs them, in
 #                 launch order, with the library's event brackets: lcm_profile_begin / lcm_profile_end)
 import contextlib
+import functools
 import threading
 
 _hooks = threading.local()
@@ -619,6 +620,62 @@ def invert_u8(x, out):
     L = _lib.load()
     _lib.check(L.lcm_invert_u8(_p(x), _p(out), int(x.numel()), _stream()), "lcm_invert_u8")
     return out
+
+
+def _resize_geometry(src, out_w, out_h, window):
+    if src.dtype != torch.uint8 or src.dim() not in (2, 3) or (src.dim() == 3 and src.shape[2] not in (1, 3)):
+        raise _lib.LcmHipError(f"resize: the source must be uint8 [H,W], [H,W,1] or [H,W,3], got {src.dtype} {tuple(src.shape)}")
+    Cn = 1 if src.dim() == 2 else int(src.shape[2])
+    x0, y0, w, h = (0, 0, out_w, out_h) if window is None else window
+    return Cn, int(src.shape[1]), int(src.shape[0]), int(out_w), int(out_h), int(x0), int(y0), int(w), int(h)
+
+
+def resize_ws_bytes(src_w, src_h, channels, out_w, out_h, window=None):
+    """Bytes of device workspace (tables, then the intermediate) that fitting a src_w x src_h picture of ``channels`` channels
+    to out_w x out_h -- or to the window (x0, y0, w, h) of that grid -- needs (lcm_resize_ws_bytes); 0 outside the domain."""
+    x0, y0, w, h = (0, 0, out_w, out_h) if window is None else window
+    return int(_lib.load().lcm_resize_ws_bytes(int(channels), int(src_w), int(src_h), int(out_w), int(out_h), int(x0), int(y0),
+                                               int(w), int(h)))
+
+
+@functools.lru_cache(maxsize=64)
+def _resize_tables(sw, sh, out_w, out_h, x0, y0, w, h):
+    """The host tables of a call (lcm_resize_plan_tables), kept per geometry in pinned memory: the upload is one async copy."""
+    L = _lib.load()
+    n = int(L.lcm_resize_plan_table_bytes(sw, sh, out_w, out_h, w, h))
+    if n <= 0:
+        raise _lib.LcmHipError(f"resize: {sw}x{sh} -> {out_w}x{out_h} window {w}x{h} is outside the resampler's domain")
+    t = torch.empty(n, dtype=torch.uint8)
+    if torch.cuda.is_available():
+        t = t.pin_memory()
+    _lib.check(L.lcm_resize_plan_tables(sw, sh, out_w, out_h, x0, y0, w, h, C.c_void_p(t.data_ptr()), n), "lcm_resize_plan_tables")
+    return t
+
+
+def resize_lanczos_u8(src, dst, ws, out_w, out_h, window=None):
+    """PIL's ``Image.resize((out_w, out_h), Image.LANCZOS)`` of the device picture src (uint8 [H,W], [H,W,1] or [H,W,3], rows
+    ``src.stride(0)`` bytes apart) into dst, byte for byte (include/lcm_hip.h, Lanczos resampler) -- or, with window =
+    (x0, y0, w, h), only that window of the out_w x out_h grid (positions outside the grid replicate its edge).  dst: a uint8
+    view of the window's shape whose rows are ``dst.stride(0)`` bytes apart, e.g. slot b of a [B,H,W,3] tensor.  ws: uint8
+    workspace of at least ``resize_ws_bytes``; its head receives the call's tables (one async copy on the current stream), then
+    at most one launch per pass follows.  Nothing is read back."""
+    L = _lib.load()
+    Cn, sw, sh, ow, oh, x0, y0, w, h = _resize_geometry(src, out_w, out_h, window)
+    want = (h, w) if dst.dim() == 2 else (h, w, Cn)
+    if dst.dtype != torch.uint8 or tuple(dst.shape) != want:
+        raise _lib.LcmHipError(f"resize: the destination must be uint8 {want}, got {dst.dtype} {tuple(dst.shape)}")
+    for t, name in ((src, "source"), (dst, "destination")):
+        inner = (1,) if t.dim() == 2 else (t.shape[2], 1)
+        if tuple(t.stride()[1:]) != inner:
+            raise _lib.LcmHipError(f"resize: the {name}'s rows must be contiguous (strides {tuple(t.stride())})")
+    tab = _resize_tables(sw, sh, ow, oh, x0, y0, w, h)
+    nbytes = int(ws.numel() * ws.element_size())
+    if nbytes < tab.numel():
+        raise _lib.LcmHipError(f"resize: workspace of {nbytes} bytes is smaller than its tables ({tab.numel()})")
+    ws.view(torch.uint8).reshape(-1)[:tab.numel()].copy_(tab, non_blocking=True)
+    _lib.check(L.lcm_resize_lanczos_u8(_p(src), int(src.stride(0)) if sh > 1 else sw * Cn, Cn, sw, sh, ow, oh, x0, y0, w, h, _p(dst),
+                                       int(dst.stride(0)) if h > 1 else w * Cn, _p(ws), nbytes, _stream()), "lcm_resize_lanczos_u8")
+    return dst
 
 
 def latents_pool8(lat, out, B, h, w):

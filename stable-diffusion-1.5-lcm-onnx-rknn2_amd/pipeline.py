@@ -141,6 +141,7 @@ class _Lane:
         self.controlnet = None        # this lane's executor of the pipeline's ControlNet (LcmHipPipeline.lane_controlnet)
         self._controlnet_of = None
         self.vae_enc = None           # this lane's executor of the VAE encoder (LcmHipPipeline.lane_vae_encoder)
+        self.fit_src = self.fit_ws = None      # uploads of another size (backends/fit.py): the raw picture and the resampler's workspace
         self.pre_ws = None            # ControlNet preprocessor (generate(preprocess=)): the Canny workspace, sized on first use
         self.enc_plans = {}           # (B, H, W) -> _EncPlan: the encoder stage of image-to-image requests
 
@@ -366,9 +367,7 @@ class LcmHipPipeline:
             raise LcmHipError("image-to-image is not served for SDXL-family UNets")
         if not 0.0 < strength <= 1.0:
             raise LcmHipError(f"image-to-image strength {strength} outside (0, 1]")
-        img = torch.as_tensor(images_u8)
-        if img.dtype != torch.uint8 or tuple(img.shape) != (B, height, width, 3):
-            raise LcmHipError(f"init images must be uint8 [B={B}, H={height}, W={width}, 3], got {img.dtype} {tuple(img.shape)}")
+        img, img_fit = self._sources(images_u8, B, (height, width, 3), "init images")
         do_cfg = self._do_cfg(guidance_scale, negative_embeds)
         ts = self.sched.timesteps(steps, strength)       # diffusers' error for steps > original_steps x strength, before any plan
         nsa, nsb = self.sched.renoise_coefficients(ts[0])
@@ -384,10 +383,11 @@ class LcmHipPipeline:
             E.h_e0[b].copy_(e0[0])
             for i, n in enumerate(rest):
                 P.h_noise[i, b].copy_(n[0])
-        E.h_img.copy_(img)
+        self._stage(E.h_img, img)
 
         def upload():
             E.img.copy_(E.h_img, non_blocking=True)
+            self._fit_pending(L, img_fit, E.img)
             E.e0.copy_(E.h_e0, non_blocking=True)
 
         def front(eager):                                # encoder -> hand-over into the strength-cut pass's state
@@ -441,11 +441,8 @@ class LcmHipPipeline:
             raise LcmHipError(f"inpainting strength {strength} outside (0, 1]")
         if not 0.0 <= mask_blur <= MAX_MASK_BLUR:
             raise LcmHipError(f"mask_blur {mask_blur} outside [0, {MAX_MASK_BLUR:g}]")
-        img, msk = torch.as_tensor(images_u8), torch.as_tensor(masks_u8)
-        if img.dtype != torch.uint8 or tuple(img.shape) != (B, height, width, 3):
-            raise LcmHipError(f"init images must be uint8 [B={B}, H={height}, W={width}, 3], got {img.dtype} {tuple(img.shape)}")
-        if msk.dtype != torch.uint8 or tuple(msk.shape) != (B, height, width):
-            raise LcmHipError(f"masks must be uint8 [B={B}, H={height}, W={width}], got {msk.dtype} {tuple(msk.shape)}")
+        img, img_fit = self._sources(images_u8, B, (height, width, 3), "init images")
+        msk, msk_fit = self._sources(masks_u8, B, (height, width), "masks")
         do_cfg = self._do_cfg(guidance_scale, negative_embeds)
         ts = self.sched.timesteps(steps, strength)       # diffusers' error for steps > original_steps x strength, before any plan
         nsa, nsb = self.sched.renoise_coefficients(ts[0])
@@ -463,13 +460,15 @@ class LcmHipPipeline:
             E.h_e0[b].copy_(e0[0])
             for i, n in enumerate(rest):
                 P.h_noise[i, b].copy_(n[0])
-        E.h_img.copy_(img)
-        P.h_mask.copy_(msk)
+        self._stage(E.h_img, img)
+        self._stage(P.h_mask, msk)
 
         def upload():
             E.img.copy_(E.h_img, non_blocking=True)
+            self._fit_pending(L, img_fit, E.img)
             E.e0.copy_(E.h_e0, non_blocking=True)
             P.mask.copy_(P.h_mask, non_blocking=True)
+            self._fit_pending(L, msk_fit, P.mask)
 
         def front(eager):                                # encoder -> mask -> hand-over into the masked pass's state
             pre_m, pre_l = self._encode_stage(L, E, eager)
@@ -971,9 +970,7 @@ class LcmHipPipeline:
             cscale = float(cscale)
             if not 0.0 <= cscale <= 2.0:
                 raise LcmHipError(f"controlnet conditioning scale {cscale} outside [0, 2]")
-            hint = torch.as_tensor(hint)
-            if hint.dtype != torch.uint8 or tuple(hint.shape) != (B, height, width, 3):
-                raise LcmHipError(f"ControlNet hint must be uint8 [B={B}, H={height}, W={width}, 3], got {hint.dtype} {tuple(hint.shape)}")
+            hint, hint_fit = self._sources(hint, B, (height, width, 3), "ControlNet hint")
         pre = tuple(preprocess) if preprocess else ()
         if pre:
             if control is None:
@@ -996,13 +993,14 @@ class LcmHipPipeline:
                 for i, n in enumerate(extra):
                     P.h_noise[i, b].copy_(n[0])
             if hint is not None:
-                P.h_hint.copy_(hint)
+                self._stage(P.h_hint, hint)
 
         def upload():
-            if hint is not None and pre:
-                self._preprocess_hint(P, pre, B, height, width)
-            elif hint is not None:
+            if hint is not None:
                 P.hint.copy_(P.h_hint, non_blocking=True)
+                self._fit_pending(P.lane, hint_fit, P.hint)      # a photo or map of another size: fitted ahead of the preprocessor
+                if pre:
+                    self._preprocess_hint(P, pre, B, height, width)
             if refine is not None and refine[2]:
                 for b in range(B):
                     P.xk[0, b].copy_(start[1][b].reshape(4, h, w), non_blocking=True)
@@ -1018,10 +1016,79 @@ class LcmHipPipeline:
             out["controlnet_evals"] = steps
         return out
 
+    @staticmethod
+    def _sources(pics, B, shape, what):
+        """The per-request uploads of a batch -> (host pictures, device fits).  pics: uint8 [B] + shape (array or tensor: every
+        picture at the request's size, the usual call), or a list of B entries, each a uint8 array of ``shape`` or a
+        ``backends.fit.Pending`` -- a picture of another size that the lane's stream is to fit (LCM_RESIZE=hip).  -> (one tensor
+        [B] + shape, None), or ([B tensors | None], [B Pending | None])."""
+        from .backends.fit import Pending
+        if isinstance(pics, (list, tuple)) and any(isinstance(p, Pending) for p in pics):
+            if len(pics) != B:
+                raise LcmHipError(f"{what}: {len(pics)} entries for a batch of {B}")
+            host, fits = [], []
+            for p in pics:
+                if isinstance(p, Pending):
+                    a = p.pixels
+                    if (a.dtype != np.uint8 or a.ndim != len(shape) or a.shape[2:] != tuple(shape[2:]) or (p.height, p.width) != tuple(shape[:2])
+                            or min(a.shape) < 1):
+                        raise LcmHipError(f"{what}: a picture to fit must be uint8 [h, w{', 3' if len(shape) == 3 else ''}] for a "
+                                          f"{shape[1]}x{shape[0]} request, got {a.dtype} {tuple(a.shape)} for {p.width}x{p.height}")
+                    host.append(None), fits.append(p)
+                else:
+                    t = torch.as_tensor(p)
+                    if t.dtype != torch.uint8 or tuple(t.shape) != tuple(shape):
+                        raise LcmHipError(f"{what} must be uint8 {list(shape)}, got {t.dtype} {tuple(t.shape)}")
+                    host.append(t), fits.append(None)
+            return host, fits
+        try:
+            t = torch.stack([torch.as_tensor(p) for p in pics]) if isinstance(pics, (list, tuple)) else torch.as_tensor(pics)
+        except (RuntimeError, TypeError, ValueError) as e:
+            raise LcmHipError(f"{what} must be uint8 {[B] + list(shape)}: {e}")
+        if t.dtype != torch.uint8 or tuple(t.shape) != (B,) + tuple(shape):
+            dims = ", ".join(f"{n}={v}" for n, v in zip("HW", shape[:2])) + (", 3" if len(shape) == 3 else "")
+            raise LcmHipError(f"{what} must be uint8 [B={B}, {dims}], got {t.dtype} {tuple(t.shape)}")
+        return t, None
+
+    @staticmethod
+    def _stage(h_buf, host):
+        """Fill the pinned staging of a batch of uploads: the whole batch, or the slots that came at the request's size."""
+        if isinstance(host, list):
+            for b, t in enumerate(host):
+                if t is not None:
+                    h_buf[b].copy_(t)
+        else:
+            h_buf.copy_(host)
+
+    def _fit_pending(self, L: _Lane, fits, dst):
+        """The uploads that came at another size, on the current (the lane's) stream, outside any captured graph: per picture the
+        raw upload into the lane's source buffer, then the Lanczos resampler (include/lcm_hip.h; csrc/resize.hip) straight into
+        slot b of dst ([B,H,W,3] or [B,H,W]).  Source buffer and workspace belong to the lane and grow on demand; they are
+        allocated on this stream, which orders every reuse behind the launches that read them.  Nothing is read back."""
+        if not fits:
+            return
+        for b, f in enumerate(fits):
+            if f is None:
+                continue
+            a = torch.from_numpy(f.pixels)
+            n = a.numel()
+            if L.fit_src is None or L.fit_src.numel() < n:
+                L.fit_src = torch.empty(n, dtype=torch.uint8, device=self.device)
+            src = L.fit_src[:n].view(a.shape)
+            src.copy_(a, non_blocking=True)
+            sh, sw = a.shape[:2]
+            win = (f.x0, f.y0, f.width, f.height)
+            need = ops.resize_ws_bytes(sw, sh, 1 if a.dim() == 2 else 3, f.fit_w, f.fit_h, win)
+            if need <= 0:
+                raise LcmHipError(f"a {sw}x{sh} picture fitted to {f.fit_w}x{f.fit_h} is outside the resampler's domain")
+            if L.fit_ws is None or L.fit_ws.numel() < need:
+                L.fit_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ops.resize_lanczos_u8(src, dst[b], L.fit_ws, f.fit_w, f.fit_h, win)
+
     def _preprocess_hint(self, P: _Plan, pre, B, H, W):
-        """The photo in P.h_hint -> the map in P.hint, on the current (the lane's) stream: the usual upload, then the preprocessor's
-        launches in place (the picture is read by the first launch only, the map written by the last).  Nothing is read back."""
-        P.hint.copy_(P.h_hint, non_blocking=True)
+        """The photo in P.hint (uploaded, and fitted where it came at another size) -> the map in P.hint, on the current (the
+        lane's) stream: the preprocessor's launches in place (the picture is read by the first launch only, the map written by
+        the last).  Nothing is read back."""
         if pre[0] == "invert":
             ops.invert_u8(P.hint, P.hint)
             return
