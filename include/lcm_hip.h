@@ -299,6 +299,23 @@ int lcm_set_attention_ksplit(int on);
 int lcm_embed_tokens_f16(const void* ids, const void* tok_emb, const void* pos_emb, void* out, int B, int S, int D,
                          int vocab, void* stream);
 
+/* ---- prompt emphasis: per-token weights on the text encoder's output, chunk mean restored (csrc/prompt.hip) ----
+ * z fp16 [n_chunks*S][D]: the encoder's output after the final LayerNorm, one 77-token chunk after the other; w fp32 [n_chunks*S]
+ * (device): the weight of every token, 1.0 at BOS, EOS and padding.  Per chunk c, with sums over ALL S x D elements e of the chunk,
+ *     S0 = sum z[e],   S1 = sum z[e] w[row(e)],   r = S1 != 0 ? S0 / S1 : 1      (= mean(z_c) / mean(z_c w): the counts cancel)
+ *     out[(c S + s) ldo + i] = fp16( (float(z) * w[c S + s]) * r )               (two fp32 products, one rounding to fp16)
+ * -- "Original" emphasis as written after A1111 (equality unverified), the mean taken per chunk of one request.  out rows have leading
+ * dimension ldo >= D (a multiple of 8), so the chunks of a request land concatenated in their slot of a wider destination; columns
+ * past D are not written.  S = 77, D in {768, 1024, 1280}; anything else is LCM_EINVAL.
+ * Reduction order (fp32; fixed, so a chunk's bits depend on neither n_chunks nor its place in the launch).  One workgroup of 512
+ * threads per chunk; the chunk's elements are numbered e = s D + i.  Thread t adds the elements 8 (t + 512 k) + j in the order
+ * k = 0, 1, ... then j = 0 .. 7:  s0 <- s0 + z,  s1 <- fma(z, w, s1).  The 64 thread sums of a wave are combined by the xor butterfly
+ * 32, 16, 8, 4, 2, 1 (v <- v + v[lane ^ o]), the 8 wave sums are then added in wave order 0 .. 7 starting from 0.  Both sums come
+ * from ONE read of the chunk (it stays in registers for the scaling).  With all weights of a chunk exactly 1.0 every fma(z, 1, s1)
+ * equals s0 + z, hence S1 == S0 bit for bit, r == 1 and out == z exactly; callers that know this on the host copy instead.
+ * No host read-back: capturable. */
+int lcm_prompt_emphasis_f16(const void* z, const void* w, void* out, int ldo, int n_chunks, int S, int D, void* stream);
+
 /* ---- row softmax in place over [rows][n] fp16 (AutoencoderKL mid-block attention, d=512 single head) ---- */
 int lcm_softmax_rows_f16(void* x, int rows, int n, int ld, void* stream);
 /* ---- [z][R][C] -> [z][C][R] transpose, fp16 ---- */

@@ -42,6 +42,7 @@ from . import fit as _fit
 from . import hires as _hires
 from . import img2img as _img2img
 from . import inpaint as _inpaint
+from . import prompt_syntax as _prompt
 from . import refine as _refine
 
 
@@ -337,7 +338,7 @@ class _Engine:
         self._stats_lock = threading.Lock()
         self.stats = dict(unet_evals=0, refine_cache_hits=0, refine_cache_misses=0, refine_cache_puts=0, controlnet_evals=0,
                           hires_requests=0, img2img_requests=0, inpaint_requests=0, controlnet_preprocessed=0,
-                          resized_on_device=0)
+                          resized_on_device=0, prompt_chunks=0, weighted_prompts=0)
         # ControlNet: where it comes from (CONTROLNET=<dir or file> | "synthetic" | None); loaded on the first request that
         # carries a hint, released with the pipeline
         self.controlnet_src = None
@@ -429,6 +430,7 @@ class _Engine:
     def run_batch(self, key, items, lane=0):
         """One batched sampler pass for ``items`` = [(req, seed[, noise])], all of ``key``, on lane ``lane``;
         -> per-item (rgb, pool8 row)."""
+        key, n_ctx = _prompt.split_ctx(key)          # a long-prompt pass: the kind's own key + ("ctx", n)
         width, height, steps, g, style_id, level = key[:6]
         import time as _t
         t0 = _t.perf_counter()
@@ -442,23 +444,23 @@ class _Engine:
             try:
                 reqs = [it[0] for it in items]
                 with torch.cuda.stream(stream):
-                    pe, kw = self.family_cls._conditioning(self, reqs, width, height, g, lane)
+                    pe, kw = self.family_cls._conditioning(self, reqs, width, height, g, lane, **({"n_ctx": n_ctx} if n_ctx > 1 else {}))
                 t1 = _t.perf_counter()
                 noises = [it[2] for it in items] if all(len(it) > 2 and it[2] is not None for it in items) else None
                 seeds = [it[1] for it in items]
                 if _hires.is_hires_key(key):         # key = plain key + (KEY_TAG, target width, target height, hr_steps, strength, mode)
                     tw, th, hr_steps, strength, mode = key[7:12]
-                    cap = pipe.hires_batch_cap(tw, th, hr_steps, strength, g, lane=lane, sizes=self.batch_sizes)
+                    cap = pipe.hires_batch_cap(tw, th, hr_steps, strength, g, lane=lane, sizes=self.batch_sizes, n_ctx=n_ctx)
                     res = self._run_capped(items, noises, pe, kw, cap, stream, "hires_requests", lambda idx, sub_pe, sub_noises, sub_kw:
                                            pipe.generate(sub_pe, [seeds[i] for i in idx], width, height, steps, g, noises=sub_noises,
                                                          lane=lane, hires=(tw, th, hr_steps, strength, mode), **sub_kw))
                 elif _img2img.is_img2img_key(key):   # key = plain key + (KEY_TAG, strength); items carry the fitted picture
-                    cap = pipe.img2img_batch_cap(width, height, steps, key[7], g, lane=lane, sizes=self.batch_sizes)
+                    cap = pipe.img2img_batch_cap(width, height, steps, key[7], g, lane=lane, sizes=self.batch_sizes, n_ctx=n_ctx)
                     res = self._run_capped(items, noises, pe, kw, cap, stream, "img2img_requests", lambda idx, sub_pe, sub_noises, sub_kw:
                                            pipe.generate_img2img(sub_pe, [seeds[i] for i in idx], _fit.stack([items[i][3] for i in idx]),
                                                                  width, height, steps, key[7], g, noises=sub_noises, lane=lane, **sub_kw))
                 elif _inpaint.is_inpaint_key(key):   # key = plain key + (KEY_TAG, strength, mask_blur); items carry picture and mask
-                    cap = pipe.inpaint_batch_cap(width, height, steps, key[7], g, lane=lane, sizes=self.batch_sizes)
+                    cap = pipe.inpaint_batch_cap(width, height, steps, key[7], g, lane=lane, sizes=self.batch_sizes, n_ctx=n_ctx)
                     res = self._run_capped(items, noises, pe, kw, cap, stream, "inpaint_requests", lambda idx, sub_pe, sub_noises, sub_kw:
                                            pipe.generate_inpaint(sub_pe, [seeds[i] for i in idx], _fit.stack([items[i][3] for i in idx]),
                                                                  _fit.stack([items[i][4] for i in idx]), width, height, steps, key[7],
@@ -596,6 +598,18 @@ class _Engine:
                 lk.release()
 
 
+_DEFAULT_CHUNKER = None
+
+
+def _default_prompt_ctx(req, guidance):
+    """Chunk count of a request for ``HipLcmWorker._job_key`` called without a worker: the synthetic runs' tokenizer."""
+    global _DEFAULT_CHUNKER
+    if _DEFAULT_CHUNKER is None:
+        from ..clip import HashTokenizer
+        _DEFAULT_CHUNKER = _prompt.PromptChunker(HashTokenizer())
+    return _DEFAULT_CHUNKER.count(getattr(req, "prompt", ""))
+
+
 _ENGINES: dict = {}              # key -> weakref.ref(_Engine)
 _ENGINES_LOCK = threading.Lock()
 
@@ -651,6 +665,7 @@ class HipLcmWorker:
                 eng = None
         if eng is not None:                          # a sibling worker already holds this checkpoint on this GPU
             self._engine = eng
+            self._bind_prompt_ctx()
             print(f"[hip] worker {worker_id} ({self.FAMILY}) attached to the resident engine on {device} ({eng.refs} workers)")
             return
         sched = LCMSchedule()
@@ -705,6 +720,7 @@ class HipLcmWorker:
         eng.refs = 1
         eng.controlnet_src, eng.synthetic_model = cn_src, bool(synthetic)
         self._engine = eng
+        self._bind_prompt_ctx()
         self._load_styles(eng)
         eng.start_batcher()
         if share:
@@ -789,25 +805,64 @@ class HipLcmWorker:
         return eng.encode.enc.weight_bytes()
 
     @staticmethod
-    def _conditioning(eng, reqs, width, height, guidance, lane=0):
-        """-> (prompt_embeds [B,77,ctx], kwargs for LcmHipPipeline.generate) for B requests of one batch."""
+    def _conditioning(eng, reqs, width, height, guidance, lane=0, n_ctx=1):
+        """-> (prompt_embeds [B,77 n,ctx], kwargs for LcmHipPipeline.generate) for B requests of one batch, n = n_ctx chunks each
+        (backends/prompt_syntax.py).  Under classifier-free guidance the requests' negative prompts are the unconditional half, and
+        the shorter of (prompt, negative prompt) is filled with empty-prompt chunks to n (A1111 with ``pad_cond_uncond`` on; its
+        default runs the two halves unpadded).  Every chunk of the pass goes through CLIP in one batch."""
         B = len(reqs)
         encode, _ = eng._lane_encoders(lane)
-        pe = encode([r.prompt for r in reqs])
-        neg = None
-        if guidance > 1.0 and not eng.pipe.unet.has_cond:
-            neg = encode([""]).expand(B, -1, -1)
+        ck, L = encode.chunker, encode.enc.L
+        do_cfg = guidance > 1.0 and not eng.pipe.unet.has_cond
+
+        def fill(c):                                 # (the cached Chunked is never touched)
+            if c.n == n_ctx:
+                return c
+            if c.n > n_ctx:
+                raise RuntimeError(f"a prompt of {c.n} chunks in a pass of {n_ctx}")
+            e_ids, e_w = ck.empty_chunk()
+            return _prompt.Chunked(c.ids + [e_ids] * (n_ctx - c.n), c.weights + [e_w] * (n_ctx - c.n), c.n_tokens)
+        texts = [fill(ck.chunk(r.prompt)) for r in reqs]
+        stops = [L - (_prompt.parse_clip_skip(r, L) - 1) for r in reqs]
+        weighted = sum(t.weighted for t in texts)
+        if do_cfg:
+            negs = [fill(ck.chunk(_prompt.negative_text(r))) for r in reqs]
+            weighted += sum(n.weighted and not t.weighted for n, t in zip(negs, texts))
+            if n_ctx == 1 and len(set(stops)) == 1 and not any(n.ids != negs[0].ids or n.weighted for n in negs):
+                # one unconditional row serves the batch (all of them are the same text, usually ""): encoded once
+                pe, n1 = encode.encode_chunked(texts, stops)
+                neg, n2 = encode.encode_chunked(negs[:1], stops[:1])
+                neg = neg.expand(B, -1, -1)
+            else:
+                both, n1 = encode.encode_chunked(negs + texts, stops + stops)
+                neg, pe, n2 = both[:B], both[B:], 0
+        else:
+            (pe, n1), neg, n2 = encode.encode_chunked(texts, stops), None, 0
+        with eng._stats_lock:
+            eng.stats["prompt_chunks"] += n1 + n2
+            eng.stats["weighted_prompts"] += weighted
         return pe, dict(negative_embeds=neg)
 
     # ------------------------------------------------------------------------------------------
     @staticmethod
-    def _job_key(req):
+    def _job_key(req, prompt_ctx=None):
         """What must agree for jobs to share one batched pass: geometry, step count, guidance and style merge -- and, for a
         refinement request (``denoise_strength`` / ``pass_number``, backends/refine.py), its strength and pass number: those
         get a key of their own (the plain fields plus (d, p)) and never share a pass with plain requests.  Hires requests
         (``enable_hr``, backends/hires.py) coalesce among themselves: the plain key + ("hires", target size, hr_steps, strength,
         mode).  Image-to-image requests (a picture, backends/img2img.py) get the plain key + ("img2img", strength); with a mask
-        (backends/inpaint.py) they are inpaint requests with the plain key + ("inpaint", strength, mask_blur) instead."""
+        (backends/inpaint.py) they are inpaint requests with the plain key + ("inpaint", strength, mask_blur) instead.
+        A prompt of n > 1 chunks (backends/prompt_syntax.py; under classifier-free guidance the longer of prompt and negative
+        prompt counts) appends ("ctx", n) to whichever of these keys the request has: the pass has 77 n context rows.  With n == 1 --
+        weighted or not, with or without a negative prompt -- the key is the one of always; the texts and ``clip_skip`` are per
+        image.  prompt_ctx(req, guidance) -> n: the engine's chunk count (a worker binds its own tokenizer, ``_bind_prompt_ctx``);
+        None: counted with the synthetic runs' stand-in tokenizer and no classifier-free guidance."""
+        key = HipLcmWorker._kind_key(req)
+        n = (prompt_ctx or _default_prompt_ctx)(req, key[3])
+        return key if n <= 1 else key + (_prompt.CTX_TAG, n)
+
+    @staticmethod
+    def _kind_key(req):
         width, height = parse_size(req.size)
         sl = getattr(req, "style_lora", None)
         style_id = getattr(sl, "style", None) if sl else None
@@ -854,6 +909,23 @@ class HipLcmWorker:
             return key + (_controlnet.KEY_TAG, ctl[0]) + _controlnet.parse_preprocessor(req)
         return key if rf is None else key + rf
 
+    def _bind_prompt_ctx(self):
+        """Give this worker's ``_job_key`` the engine's own chunk count: its tokenizer, its text encoder's depth (clip_skip is
+        checked there, for its own job) and whether guidance above 1 means a negative prompt is encoded."""
+        eng = self._engine
+        if eng.encode is None:                       # SDXL: two encoders, prompts truncated to 77 tokens as ever
+            return
+        ck, L, cfg_capable = eng.encode.chunker, eng.encode.enc.L, not eng.pipe.unet.has_cond
+        base = HipLcmWorker.__dict__["_job_key"].__func__
+
+        def prompt_ctx(req, guidance):
+            _prompt.parse_clip_skip(req, L)
+            n = ck.count(getattr(req, "prompt", ""))
+            if cfg_capable and guidance > 1.0:
+                n = max(n, ck.count(_prompt.negative_text(req)))
+            return n
+        self._job_key = lambda req: base(req, prompt_ctx)
+
     def _run_batch(self, key, items):
         return self._engine.run_batch(key, items)
 
@@ -868,6 +940,7 @@ class HipLcmWorker:
         An upload that does not have the request's size is fitted here on the host (LCM_RESIZE=pil, or outside the device path's
         domain) or handed on at its own size as a ``fit.Pending`` for the lane's stream to fit (backends/fit.py)."""
         eng = self._engine
+        key, _ = _prompt.split_ctx(key)              # the prompt's length changes nothing here
         seed = int(req.seed) if getattr(req, "seed", None) is not None else int(torch.randint(0, 100_000_000, (1,)).item())
         # the request's RNG stream (initial latents, then one draw per remaining step) is drawn HERE, on the caller's
         # thread: pool threads do it in parallel and the GPU dispatcher's serial path shrinks by ~0.5 ms per request
@@ -1137,7 +1210,7 @@ class HipLcmSDXLWorker(HipLcmWorker):
             raise RuntimeError("init_image: image-to-image is not served by the SDXL worker (SD1.5 and SD 2.x only)")
         if getattr(req, "mask", None) is not None or getattr(req, "mask_image", None) is not None:
             raise RuntimeError("mask: inpainting is not served by the SDXL worker (SD1.5 and SD 2.x only)")
-        return HipLcmWorker._job_key(req)
+        return HipLcmWorker._kind_key(req)           # prompts are truncated to 77 tokens here, as ever: no ("ctx", n)
 
     def _synthetic_weights(self):
         from ..config import SDXL_UNET, unet_config, vae_config

@@ -141,7 +141,11 @@ class RefineCache:
 
 def request_ident(req, key, seed):
     """What x^k of a request depends on besides (d, k): prompt, seed, size, steps, guidance, style, level."""
-    return (req.prompt, int(seed)) + tuple(key[:6])
+    # (a negative prompt or a clip_skip other than 1 changes x^k too; requests without them keep the identity of always)
+    ov = getattr(req, "override_settings", None)
+    more = (getattr(req, "negative_prompt", None) or "", getattr(req, "clip_skip", None) or 1,
+            (ov.get("CLIP_stop_at_last_layers") if isinstance(ov, dict) else None) or 1)
+    return (req.prompt, int(seed)) + tuple(key[:6]) + (more if more != ("", 1, 1) else ())
 
 
 def group_by_start(starts, sizes):

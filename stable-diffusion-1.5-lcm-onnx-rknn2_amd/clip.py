@@ -136,36 +136,44 @@ class ClipTextHip:
         return v
 
     @torch.inference_mode()
-    def forward(self, ids: torch.Tensor, output="last", pooled=False):
+    def forward(self, ids: torch.Tensor, output="last", pooled=False, stop=None, keep=False):
         """ids: int [B, S<=77] (host or device).
         output="last": final_layer_norm(last layer)           -> fp16 [B, S, D]   (SD1.5: last_hidden_state)
         output="penultimate": hidden_states[-2], no final LN   -> fp16 [B, S, D]   (SDXL, both encoders)
         pooled=True additionally returns text_projection(final_layer_norm(last layer)[EOS token]) fp16 [B, P]
         (CLIPTextModelWithProjection.text_embeds; EOS = position of the largest id, as transformers does for CLIP).
+        stop (output="last" only): the number of layers to run before the final LayerNorm, 1 .. L; None = L.  A request's
+        ``clip_skip = k`` is stop = L - (k - 1): the hidden state after that layer goes through final_layer_norm (A1111's
+        CLIP_stop_at_last_layers).  stop = L is the call without it: same launches, same graph, same bits.
+        keep: return the encoder's own [B, S, D] buffer instead of a copy -- valid until the next call on this view.
 
-        The SD1.5 form (output="last", no pooled vector) replays a hipGraph per (B, S): 86 launches through ctypes cost the
+        The SD1.5 form (output="last", no pooled vector) replays a hipGraph per (B, S, stop): 86 launches through ctypes cost the
         request's thread ~1 ms, one graph launch ~0.05 (LCM_CLIP_GRAPH=0: always eager).  Same kernels, same launch
         parameters, same bits."""
         B, S = ids.shape
+        stop = self.L if stop is None else int(stop)
+        if not 1 <= stop <= self.L or (stop != self.L and (output != "last" or pooled)):
+            raise ValueError(f"stop layer {stop}: expected 1 .. {self.L}, and only with output='last' without the pooled vector")
         # (the legacy default stream cannot be captured: callers outside a lane's stream run eagerly)
         if CLIP_GRAPH and output == "last" and not pooled and torch.cuda.current_stream(self.device) != torch.cuda.default_stream(self.device):
-            key = (B, S)
-            ids_d = self._ids.get(key)
+            key = (B, S, stop)
+            ids_d = self._ids.get((B, S))
             if ids_d is None:
-                ids_d = self._ids[key] = torch.empty(B, S, dtype=torch.int32, device=self.device)
+                ids_d = self._ids[(B, S)] = torch.empty(B, S, dtype=torch.int32, device=self.device)
             ids_d.copy_(ids.to(dtype=torch.int32), non_blocking=False)
             g = self._graphs.get(key)
             if g is None:
-                self._encode(ids_d, B, S, "last")                  # eager once: allocates the activation buffers
+                self._encode(ids_d, B, S, "last", layers=stop)     # eager once: allocates the activation buffers
                 g = ops.Graph()
                 with g:
-                    self._encode(ids_d, B, S, "last")
+                    self._encode(ids_d, B, S, "last", layers=stop)
                 self._graphs[key] = g
             g.launch()
-            return self._b("fin", B * S, self.D).reshape(B, S, self.D).clone()     # the buffer belongs to the next call
+            fin = self._b("fin", B * S, self.D).reshape(B, S, self.D)
+            return fin if keep else fin.clone()                    # the buffer belongs to the next call
         ids_d = ids.to(device=self.device, dtype=torch.int32).contiguous()
-        hidden, fin = self._encode(ids_d, B, S, output, want_fin=pooled)
-        if output == "last":
+        hidden, fin = self._encode(ids_d, B, S, output, want_fin=pooled, layers=stop)
+        if output == "last" and not keep:
             hidden = hidden.clone()
         if not pooled:
             return hidden
@@ -181,9 +189,9 @@ class ClipTextHip:
             ops.linear_smallm(rows[b0:b0 + nb], self.w["proj"], te[b0:b0 + nb], nb, P, D)
         return hidden, te
 
-    def _encode(self, ids_d, B, S, output, want_fin=False):
+    def _encode(self, ids_d, B, S, output, want_fin=False, layers=None):
         """The kernel sequence (what a graph captures).  -> (hidden [B,S,D], final-LN rows [M,D] or None); both in buffers
-        of this view."""
+        of this view.  layers: how many of the L layers run (forward's ``stop``); None = all."""
         D, F, H = self.D, self.F, self.heads
         M, d = B * S, D // H
         w = self.w
@@ -193,6 +201,8 @@ class ClipTextHip:
         pooled = want_fin
         pen = None
         last_needed = self.L if (output == "last" or pooled) else self.L - 1
+        if layers is not None:
+            last_needed = min(last_needed, int(layers))
         for i in range(last_needed):
             if output == "penultimate" and i == self.L - 1:
                 pen = x.clone()                                    # hidden_states[-2]: input of the last layer (device copy)
@@ -223,6 +233,12 @@ class HashTokenizer:
 
     def __init__(self, vocab_size=49408, bos=49406, eos=49407):
         self.vocab, self.bos, self.eos = vocab_size, bos, eos
+        self.pad = eos
+        self.comma = self.encode_text(",")[0]       # a comma standing alone as a word (backends/prompt_syntax.py)
+
+    def encode_text(self, text):
+        """The ids of the words of ``text``, no BOS / EOS, no padding or truncation: what __call__ puts between BOS and EOS."""
+        return [zlib.crc32(w.encode("utf-8")) % (self.bos - 1) + 1 for w in str(text).lower().split()]
 
     def __call__(self, prompts):
         rows = []

@@ -283,9 +283,13 @@ class _UNetEncoder(_Net):
 
     # ---- per request: cross-attention K/V of all 16 layers (depend on the prompt only) -------
     def encode_context(self, ehs, B):
-        """ehs: fp16 [B*77, ctx] -> kv_all [B*77, kv_total]."""
-        kv = self.buf.get("kv_all", B * TEXT_SEQ_LEN, self.kv_total)
-        ops.gemm(ehs, self.w["kv_all.w"], kv, img_rows=TEXT_SEQ_LEN)
+        """ehs: fp16 [B*Sk, ctx] -> kv_all [B*Sk, kv_total]; Sk = 77 n: the n chunks of a prompt, concatenated (n = 1: today's
+        buffer, today's launch)."""
+        Sk = ehs.shape[0] // B
+        if Sk * B != ehs.shape[0] or Sk % TEXT_SEQ_LEN:
+            raise ValueError(f"encode_context: {ehs.shape[0]} context rows are not {B} x a multiple of {TEXT_SEQ_LEN}")
+        kv = self.buf.get("kv_all", B * Sk, self.kv_total)
+        ops.gemm(ehs, self.w["kv_all.w"], kv, img_rows=Sk)
         return kv
 
     # ---- per step: time embedding MLP + all time_emb_proj (depend on t and guidance only) ----
@@ -359,6 +363,7 @@ class _UNetEncoder(_Net):
     def transformer(self, p, x, C, B, H, W, kv_all, out_role, x_st=None, heads=8, depth=1):
         w = self.w
         HW, M, d = H * W, B * H * W, C // heads
+        Sk = kv_all.shape[0] // B                      # 77 n context rows per image (encode_context)
         hn = self.buf.get("gn", M, C)
         self.norm(x, w[p + ".norm.g"], w[p + ".norm.b"], hn, B, HW, C, x_st=x_st, eps=1e-6, silu=False)
         h = self.buf.get("tf_h", M, C)
@@ -375,7 +380,7 @@ class _UNetEncoder(_Net):
             ops.gemm(a, w[q + ".o1.w"], h, bias=w[q + ".o1.b"], res=h, img_rows=HW)
             ops.gemm_ln(h, w[q + ".q2.w"], w[q + ".q2.g"], w[q + ".q2.c"], q2, img_rows=HW)
             off, _ = self.kv_off[q]
-            ops.attention(q2, kv_all[:, off:off + C], kv_all[:, off + C:off + 2 * C], a, B, heads, HW, TEXT_SEQ_LEN, d,
+            ops.attention(q2, kv_all[:, off:off + C], kv_all[:, off + C:off + 2 * C], a, B, heads, HW, Sk, d,
                           ldq=C, ldk=self.kv_total, ldv=self.kv_total, ldo=C, scale=0.0)
             ops.gemm(a, w[q + ".o2.w"], h, bias=w[q + ".o2.b"], res=h, img_rows=HW)
             if ops.mlp_fused_applies(M, C, HW):

@@ -425,6 +425,17 @@ def embed_tokens(ids, tok_emb, pos_emb, out, B, S, D):
     return out
 
 
+def prompt_emphasis(z, w, out, n_chunks, S, D, ldo=None):
+    """out rows <- fp16(z * w[row] * mean(z_c) / mean(z_c * w)) per 77-token chunk c (lcm_prompt_emphasis_f16): z fp16
+    [n_chunks*S, D], w fp32 [n_chunks*S] on the device, out fp16 rows of leading dimension ldo (default: out's row stride)."""
+    L = _lib.load()
+    ldo = out.stride(0) if ldo is None else ldo
+    _lib.check(L.lcm_prompt_emphasis_f16(_p(z), _p(w), _p(out), int(ldo), int(n_chunks), int(S), int(D), _stream()),
+               "lcm_prompt_emphasis_f16")
+    _record_plain(lambda: prompt_emphasis(z, w, out, n_chunks, S, D, ldo))
+    return out
+
+
 def attention(q, k, v, out, B, heads, Sq, Sk, d, *, ldq, ldk, ldv, ldo, scale=None, causal=False):
     """scale None: d^-0.5.  scale 0: q already carries scale * log2(e) (folded into the to_q weights, model._pack_transformer)."""
     L = _lib.load()

@@ -156,7 +156,7 @@ class _Plan:
 
     FROM_STATE = ("from-state", "inpaint")
 
-    def __init__(self, pipe, B, h, w, steps, do_cfg, lane=None, refine=None, control=None, kind=None):
+    def __init__(self, pipe, B, h, w, steps, do_cfg, lane=None, refine=None, control=None, kind=None, n_ctx=1):
         # Every zero-fill below must be ordered before the first use on the lane's (non-blocking) stream: allocate
         # under that stream, or a fill still queued on the null stream can land AFTER the request's uploads.
         self.lane = lane if lane is not None else pipe.lanes[0]
@@ -164,6 +164,7 @@ class _Plan:
         self.control = control        # conditioning scale of a ControlNet plan (baked into the captured GEMMs); None: no hint
         self.kind = kind              # None | "latents" | "from-state" (the stages of a hires request) | "inpaint"
         self.init_img = None          # inpaint: the encoder stage's picture buffer (uint8 [B,H,W,3]), set by generate_inpaint
+        self.n_ctx = int(n_ctx)       # 77-token chunks of the prompt: the cross-attention context is 77 n_ctx rows per image
         with torch.cuda.stream(self.lane.stream):
             self._init(pipe, B, h, w, steps, do_cfg)
 
@@ -172,7 +173,7 @@ class _Plan:
         self.B, self.h, self.w, self.steps, self.do_cfg = B, h, w, steps, do_cfg
         UB = 2 * B if do_cfg else B
         self.UB = UB
-        self.ehs = torch.zeros(UB * TEXT_SEQ_LEN, pipe.unet.ctx_dim, dtype=torch.float16, device=dev)
+        self.ehs = torch.zeros(UB * TEXT_SEQ_LEN * self.n_ctx, pipe.unet.ctx_dim, dtype=torch.float16, device=dev)
         self.wemb = torch.zeros(UB, pipe.unet.cfg.get("time_cond_proj_dim") or 8, dtype=torch.float16, device=dev)
         self.add_in = (torch.zeros(UB, pipe.unet.added_dim, dtype=torch.float16, device=dev)
                        if pipe.unet.has_added else None)          # SDXL: [pooled text embeds | sinusoid(time ids)]
@@ -372,7 +373,7 @@ class LcmHipPipeline:
         ts = self.sched.timesteps(steps, strength)       # diffusers' error for steps > original_steps x strength, before any plan
         nsa, nsb = self.sched.renoise_coefficients(ts[0])
         h, w = height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR
-        P = self._from_state_plan(B, width, height, steps, strength, guidance_scale, lane)
+        P = self._from_state_plan(B, width, height, steps, strength, guidance_scale, lane, n_ctx=self._n_ctx(pe))
         L = P.lane
         self.lane_vae_encoder(L)                         # raises for a checkpoint without an encoder, before anything is queued
         E = self._enc_plan(L, B, height, width)
@@ -447,7 +448,7 @@ class LcmHipPipeline:
         ts = self.sched.timesteps(steps, strength)       # diffusers' error for steps > original_steps x strength, before any plan
         nsa, nsb = self.sched.renoise_coefficients(ts[0])
         h, w = height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR
-        P = self._from_state_plan(B, width, height, steps, strength, guidance_scale, lane, kind="inpaint")
+        P = self._from_state_plan(B, width, height, steps, strength, guidance_scale, lane, kind="inpaint", n_ctx=self._n_ctx(pe))
         L = P.lane
         self.lane_vae_encoder(L)                         # raises for a checkpoint without an encoder, before anything is queued
         E = self._enc_plan(L, B, height, width)
@@ -588,7 +589,7 @@ class LcmHipPipeline:
             ops.inpaint_composite_rgb8(P.rgb, P.init_img, P.alpha, B, h * VAE_SCALE_FACTOR, w * VAE_SCALE_FACTOR)
         return state
 
-    def plan(self, B, h, w, steps, do_cfg=False, guidance=None, lane=0, refine=None, control=None, kind=None) -> _Plan:
+    def plan(self, B, h, w, steps, do_cfg=False, guidance=None, lane=0, refine=None, control=None, kind=None, n_ctx=1) -> _Plan:
         # classifier-free guidance bakes the guidance value into the captured step kernels: one plan per value
         key = (B, h, w, steps, do_cfg, round(float(guidance), 4) if do_cfg and guidance is not None else None)
         if refine is not None:                       # (d, passes to run, starts from cached latents): a chain of its own
@@ -597,6 +598,8 @@ class LcmHipPipeline:
             key = key + ("control", round(float(control), 6))
         if kind is not None:                         # a stage of a hires request: "latents" (no decode) / "from-state"; "inpaint"
             key = key + (kind,)
+        if int(n_ctx) != 1:                          # a long prompt: 77 n_ctx context rows (other buffers, other launches)
+            key = key + ("ctx", int(n_ctx))
         L = self.lane(lane)
         P = L.plans.get(key)
         if P is None:
@@ -604,7 +607,7 @@ class LcmHipPipeline:
                 P = L.plans.get(key)
                 if P is None:
                     P = _Plan(self, B, h, w, steps, do_cfg, L, refine=refine,
-                              control=None if control is None else round(float(control), 6), kind=kind)
+                              control=None if control is None else round(float(control), 6), kind=kind, n_ctx=n_ctx)
                     L.plans[key] = P
         return P
 
@@ -670,12 +673,12 @@ class LcmHipPipeline:
     def _upload_text(self, P: _Plan, pe, negative_embeds, guidance_scale):
         """Prompt embeddings (negative ones in front under classifier-free guidance) and the guidance embedding into the plan's
         buffers, on the current stream."""
-        B = P.B
-        pe16 = pe.to(torch.float16).reshape(B * TEXT_SEQ_LEN, -1)
+        B, rows = P.B, P.B * TEXT_SEQ_LEN * P.n_ctx
+        pe16 = pe.to(torch.float16).reshape(rows, -1)
         if P.do_cfg:
-            ne16 = torch.as_tensor(negative_embeds).to(torch.float16).reshape(B * TEXT_SEQ_LEN, -1)
-            P.ehs[:B * TEXT_SEQ_LEN].copy_(ne16, non_blocking=True)
-            P.ehs[B * TEXT_SEQ_LEN:].copy_(pe16, non_blocking=True)
+            ne16 = torch.as_tensor(negative_embeds).to(torch.float16).reshape(rows, -1)
+            P.ehs[:rows].copy_(ne16, non_blocking=True)
+            P.ehs[rows:].copy_(pe16, non_blocking=True)
         else:
             P.ehs.copy_(pe16, non_blocking=True)
         if self.unet.has_cond:
@@ -722,11 +725,19 @@ class LcmHipPipeline:
             raise LcmHipError("classifier-free guidance needs negative_embeds")
         return do_cfg
 
-    def _from_state_plan(self, B, width, height, steps, strength, guidance_scale, lane, kind="from-state") -> _Plan:
+    @staticmethod
+    def _n_ctx(pe) -> int:
+        """Chunks of a request's prompt embeddings [B, 77 n, ctx]."""
+        rows = pe.shape[1] if pe.dim() == 3 else 0
+        if rows < TEXT_SEQ_LEN or rows % TEXT_SEQ_LEN:
+            raise LcmHipError(f"prompt embeddings of shape {tuple(pe.shape)}: expected [B, {TEXT_SEQ_LEN} n, ctx]")
+        return rows // TEXT_SEQ_LEN
+
+    def _from_state_plan(self, B, width, height, steps, strength, guidance_scale, lane, kind="from-state", n_ctx=1) -> _Plan:
         """The plan of one strength-cut pass that starts from a state the hand-over launch of a front stage wrote (hires
         stage 2, image-to-image; kind "inpaint": the masked pass of an inpaint request)."""
         return self.plan(B, height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR, int(steps), self._do_cfg(guidance_scale),
-                         guidance_scale, lane=lane, refine=(float(strength), 1, True), kind=kind)
+                         guidance_scale, lane=lane, refine=(float(strength), 1, True), kind=kind, n_ctx=n_ctx)
 
     def _recorded_need(self, holder, L: _Lane, run) -> int:
         """_need_of one eager run() recorded on the lane's stream; remembered on ``holder`` (a plan)."""
@@ -773,31 +784,31 @@ class LcmHipPipeline:
         enc = self.lane_vae_encoder(L)
         return self._recorded_need(E, L, lambda: enc.encode(E.img, 1, height, width))
 
-    def _batch_cap(self, width, height, steps, strength, guidance_scale, lane, sizes, other_need=0) -> int:
+    def _batch_cap(self, width, height, steps, strength, guidance_scale, lane, sizes, other_need=0, n_ctx=1) -> int:
         """The largest pass size of ``sizes`` at which the from-state pass at width x height -- and a stage of ``other_need``
         bytes per request before it on the same stream -- fits the lane's split-K workspace (at least the smallest: a batch-1
         pass that does not fit raises the library's loud error when it runs)."""
-        P = self._from_state_plan(1, width, height, steps, strength, guidance_scale, lane)
+        P = self._from_state_plan(1, width, height, steps, strength, guidance_scale, lane, n_ctx=n_ctx)
         per_request = max(self.splitk_need(P) * (2 if P.do_cfg else 1), other_need)   # classifier-free guidance: two UNet rows
         fit = [n for n in sorted(sizes) if n * per_request <= P.lane.splitk_ws.numel() * 4]
         return fit[-1] if fit else min(sizes)
 
-    def img2img_batch_cap(self, width, height, steps, strength, guidance_scale=1.0, lane=0, sizes=(1, 2, 4, 8)) -> int:
+    def img2img_batch_cap(self, width, height, steps, strength, guidance_scale=1.0, lane=0, sizes=(1, 2, 4, 8), n_ctx=1) -> int:
         """The largest pass size of ``sizes`` at which BOTH stages of an image-to-image request at width x height fit the lane's
         split-K workspace: the strength-cut pass (hires_batch_cap's count, doubled rows under classifier-free guidance) and the
         encoder stage.  The stages run one after the other on one stream, so the need is the larger of the two."""
         return self._batch_cap(width, height, steps, strength, guidance_scale, lane, sizes,
-                               self.encoder_splitk_need(width, height, lane))
+                               self.encoder_splitk_need(width, height, lane), n_ctx=n_ctx)
 
-    def inpaint_batch_cap(self, width, height, steps, strength, guidance_scale=1.0, lane=0, sizes=(1, 2, 4, 8)) -> int:
+    def inpaint_batch_cap(self, width, height, steps, strength, guidance_scale=1.0, lane=0, sizes=(1, 2, 4, 8), n_ctx=1) -> int:
         """img2img_batch_cap for an inpaint request: its masked pass runs the same contractions as the image-to-image pass (the
         plan it asks is the image-to-image one) and the same encoder stage; the mask launches need no split-K workspace."""
-        return self.img2img_batch_cap(width, height, steps, strength, guidance_scale, lane, sizes)
+        return self.img2img_batch_cap(width, height, steps, strength, guidance_scale, lane, sizes, n_ctx=n_ctx)
 
-    def hires_batch_cap(self, width, height, hr_steps, strength, guidance_scale=1.0, lane=0, sizes=(1, 2, 4, 8)) -> int:
+    def hires_batch_cap(self, width, height, hr_steps, strength, guidance_scale=1.0, lane=0, sizes=(1, 2, 4, 8), n_ctx=1) -> int:
         """The largest pass size of ``sizes`` whose second stage at width x height fits the lane's split-K workspace (at least
         the smallest: a batch-1 pass that does not fit raises the library's loud error when it runs)."""
-        return self._batch_cap(width, height, hr_steps, strength, guidance_scale, lane, sizes)
+        return self._batch_cap(width, height, hr_steps, strength, guidance_scale, lane, sizes, n_ctx=n_ctx)
 
     def _run_plan(self, P: _Plan, guidance_scale, eager, want_float=False, taps=None):
         """Run the plan now, on the current stream: plain launches under the build lock (they allocate scratch), or its graph."""
@@ -873,8 +884,9 @@ class LcmHipPipeline:
         ts2 = self.sched.timesteps(hr_steps, strength)   # diffusers' error for hr_steps > original_steps x strength, before any plan
         nsa, nsb = self.sched.renoise_coefficients(ts2[0])
         h, w, h2, w2 = height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR, H2 // VAE_SCALE_FACTOR, W2 // VAE_SCALE_FACTOR
-        P1 = self.plan(B, h, w, steps, do_cfg, guidance_scale, lane=lane, kind="latents")
-        P2 = self._from_state_plan(B, W2, H2, hr_steps, strength, guidance_scale, lane)
+        n_ctx = self._n_ctx(pe)
+        P1 = self.plan(B, h, w, steps, do_cfg, guidance_scale, lane=lane, kind="latents", n_ctx=n_ctx)
+        P2 = self._from_state_plan(B, W2, H2, hr_steps, strength, guidance_scale, lane, n_ctx=n_ctx)
         for b, s in enumerate(seeds):
             l0, lo, hi = noises[b] if noises is not None else draw_noise_hires(s, h, w, steps, h2, w2, hr_steps,
                                                                                self.sched.init_noise_sigma)
@@ -903,7 +915,8 @@ class LcmHipPipeline:
     def generate(self, prompt_embeds, seeds, width, height, steps, guidance_scale=1.0, negative_embeds=None,
                  want_float=False, taps=None, latents=None, added=None, negative_added=None, noises=None, lane=0,
                  strength=None, passes=0, start=None, control=None, hires=None, preprocess=None):
-        """prompt_embeds: [B,77,ctx] (any float dtype, host or device); seeds: B ints.  noises: optional per-request
+        """prompt_embeds: [B,77 n,ctx] (any float dtype, host or device; n chunks of a long prompt, concatenated: the
+        plan, its graph and its cross-attention launches are those of n -- n = 1 is the plan of always); seeds: B ints.  noises: optional per-request
         ``draw_noise(seed, h, w, steps - 1, init_noise_sigma)`` results drawn ahead by the callers (the worker's pool
         threads draw them in parallel, off the dispatcher's serial path); None: drawn here from the seeds.
         lane: which of the pipeline's concurrent sampler instances runs the request (calls on different lanes may overlap;
@@ -977,7 +990,7 @@ class LcmHipPipeline:
                 raise LcmHipError("a ControlNet preprocessor needs a hint to work on (control=)")
             if not ((pre[0] == "canny" and len(pre) == 3) or pre == ("invert",)):
                 raise LcmHipError(f"unknown ControlNet preprocessor {pre!r}: expected ('canny', low, high) or ('invert',)")
-        P = self.plan(B, h, w, steps, do_cfg, guidance_scale, lane=lane, refine=refine, control=cscale)
+        P = self.plan(B, h, w, steps, do_cfg, guidance_scale, lane=lane, refine=refine, control=cscale, n_ctx=self._n_ctx(pe))
         with torch.cuda.stream(P.lane.stream):       # latents= and the hint may be device tensors
             for b, s in enumerate(seeds):
                 if latents is not None:

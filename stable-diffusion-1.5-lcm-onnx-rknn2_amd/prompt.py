@@ -15,6 +15,8 @@ import os
 
 import torch
 
+from . import ops
+from .backends.prompt_syntax import PromptChunker
 from .clip import ClipTextHip, HashTokenizer, load_clip_dir, synthetic_clip
 from .config import TEXT_SEQ_LEN
 
@@ -23,6 +25,14 @@ class _BpeTokenizer:
     def __init__(self, d: str):
         from transformers import CLIPTokenizer
         self.tok = CLIPTokenizer.from_pretrained(d)
+        # what backends/prompt_syntax.py needs: the ids a chunk is framed and filled with (the directory's own pad id, as the call
+        # below pads) and the comma a chunk may be cut at
+        self.bos, self.eos, self.pad = self.tok.bos_token_id, self.tok.eos_token_id, self.tok.pad_token_id
+        self.comma = self.tok.get_vocab().get(",</w>", -1)
+
+    def encode_text(self, text):
+        """The ids of ``text`` without BOS / EOS, padding or truncation: what __call__ puts between BOS and EOS."""
+        return self.tok.encode(str(text), add_special_tokens=False, truncation=False, verbose=False)
 
     def __call__(self, prompts):
         ids = self.tok(list(prompts), padding="max_length", max_length=TEXT_SEQ_LEN, truncation=True,
@@ -76,5 +86,47 @@ class HipPromptEncoder:
         self.enc = ClipTextHip(sd, cfg, device=device)
         self.tokenize = make_tokenizer(ckpt_root, "tokenizer", self.enc.cfg["vocab_size"], self.source != "synthetic")
 
+        self.chunker = PromptChunker(self.tokenize)
+
     def __call__(self, prompts):
         return self.enc.forward(self.tokenize(prompts))
+
+    @torch.inference_mode()
+    def encode_chunked(self, texts, stops=None):
+        """texts: one ``prompt_syntax.Chunked`` per output row, all of the same chunk count n; stops: the text encoder's stop layer
+        per row (None: all layers).  -> (fp16 [len(texts), 77 n, D] on the device, chunks encoded).  All chunks of rows that share
+        a stop layer go through CLIP as ONE batch (CLIP batches are batch-invariant); lcm_prompt_emphasis_f16 then writes the rows
+        that carry weights into their slot of the result, and rows whose weights are all 1.0 are copied there (an exact skip,
+        decided here on the host).  A batch of plain one-chunk rows with one stop layer is the call above: same launches, same
+        bits."""
+        enc = self.enc
+        R, n, D = len(texts), texts[0].n, enc.D
+        if any(t.n != n for t in texts):
+            raise ValueError("encode_chunked: every row of a pass has the same number of chunks")
+        stops = [enc.L if s is None else int(s) for s in (stops or [None] * R)]
+        if n == 1 and len(set(stops)) == 1 and not any(t.weighted for t in texts):
+            ids = torch.tensor([t.ids[0] for t in texts], dtype=torch.int32)
+            return enc.forward(ids, stop=stops[0]), R
+        out = torch.empty(R, n * TEXT_SEQ_LEN, D, dtype=torch.float16, device=enc.device)
+        flat = out.reshape(R * n * TEXT_SEQ_LEN, D)
+        for stop in sorted(set(stops), reverse=True):
+            rows = [r for r in range(R) if stops[r] == stop]
+            ids = torch.tensor([c for r in rows for c in texts[r].ids], dtype=torch.int32)
+            z = enc.forward(ids, stop=stop, keep=True).reshape(len(rows) * n * TEXT_SEQ_LEN, D)
+            w_d = None
+            if any(texts[r].weighted for r in rows):
+                w_d = torch.tensor([w for r in rows for c in texts[r].weights for w in c], dtype=torch.float32).to(enc.device, non_blocking=True)
+            # spans of rows that are neighbours in the result and alike in carrying weights: one launch, or one copy, each
+            i = 0
+            while i < len(rows):
+                j, wt = i + 1, texts[rows[i]].weighted
+                while j < len(rows) and rows[j] == rows[j - 1] + 1 and texts[rows[j]].weighted == wt:
+                    j += 1
+                a, b = i * n * TEXT_SEQ_LEN, j * n * TEXT_SEQ_LEN
+                dst = flat[rows[i] * n * TEXT_SEQ_LEN:(rows[i] + j - i) * n * TEXT_SEQ_LEN]
+                if wt:
+                    ops.prompt_emphasis(z[a:b], w_d[a:b], dst, (j - i) * n, TEXT_SEQ_LEN, D)
+                else:
+                    dst.copy_(z[a:b])
+                i = j
+        return out, R * n
