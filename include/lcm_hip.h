@@ -468,6 +468,47 @@ int lcm_canny_rgb8(const void* in_rgb, void* out_rgb, void* ws, long long ws_byt
                    void* stream);
 int lcm_invert_u8(const void* in, void* out, long long n, void* stream);
 
+/* ---- variation seeds: subseed blend and seed-resize paste of the initial latents (csrc/variation.hip, DESIGN.md sections 3, 6) ----
+ * The text below DEFINES the result.  It was written after A1111's create_random_tensors / slerp as recalled; equality with A1111
+ * is UNVERIFIED, and two deviations are deliberate (below).
+ *   lat0 fp32 [B][4][h][w]: the requests' initial latents (the target).  Slot b has a descriptor d = descs[b] (a HOST array of B,
+ *   copied into the kernel's arguments: nothing of it is read after the call returns):
+ *     active == 0: the slot is not touched and the other fields are not read.
+ *     low, high fp32 [4][hs][ws] (device): the base noise and the subseed's noise at the SOURCE shape; t in [0, 1].
+ *   Blend, per channel c and source column x, over the hs values down the HEIGHT axis (A1111's quirk, kept: the sphere is per
+ *   column), all in fp32:
+ *     S_ll = sum low^2,  S_hh = sum high^2,  S_lh = sum low high    -- each s <- fma(a, b, s) from 0 over y = 0, 1, ..., hs - 1
+ *     d = S_lh / sqrt(S_ll * S_hh)
+ *     if S_ll > 0 and S_hh > 0 and |d| <= 0.9995 (false for a NaN):   w = acos(d), so = sin(w),
+ *         a = sin((1 - t) w) / so,  b = sin(t w) / so                 (IEEE division: b == 1 exactly at t == 1, a == 1 at t == 0)
+ *     else  a = 1 - t,  b = t                                         (zero, parallel and antiparallel columns: linear)
+ *     r[c][y][x] = fma(a, low[c][y][x], b * high[c][y][x])
+ *   t == 0: nothing is blended and high is not read (may be NULL): r = low bit for bit.
+ *   Deviations from A1111: it takes the linear branch for the WHOLE tensor on mean(d) > 0.9995, with the two weights swapped, and
+ *   returns NaN for an exactly parallel column; here the rule is per column, the weights are the right way round and no finite
+ *   input gives a NaN.
+ *   Paste (seed-resize): r is centred into the slot.  dx = floor((w - ws) / 2), dy = floor((h - hs) / 2).  On an axis where the
+ *   source is not larger, the whole of r lands at offset dx (dy); where it is larger, its window from -dx (-dy) of the target's
+ *   size fills the whole axis.  The axes are independent.  The sums always run over ALL hs rows of the source column, also those
+ *   the paste crops.  Cells of the slot outside the window keep their value.
+ *   In place: low may be the slot itself (then hs == h and ws == w are required): every thread owns whole columns and has read a
+ *   cell before it writes it.  Otherwise low and high must not overlap the slot.
+ * One launch for the whole batch: one wave of 64 threads per (slot, 64 (channel, column) pairs); a thread walks its column twice
+ * (sums, then blend), lanes are neighbouring columns, so loads coalesce across x.  No workgroup waits for another, no LDS.  A
+ * column's bits depend on its own low, high and t only -- not on B, the slot, the lane or the other requests.
+ * LCM_EINVAL before anything is enqueued: null lat0 / descs, B outside 1..8, h, w, hs or ws outside 1..256, t outside [0, 1] or NaN,
+ * a null or non-4-byte-aligned low (or high with t > 0), a low that overlaps the slot without being it.  No active slot: LCM_OK
+ * and no launch.  Nothing allocates or synchronises; capturable. */
+typedef struct lcm_variation_desc {
+    const void* low;           /* fp32 [4][hs][ws]; the slot itself for a blend in place */
+    const void* high;          /* fp32 [4][hs][ws]; not read when t == 0 */
+    int hs, ws;                /* source shape, 1..256 each */
+    float t;                   /* subseed strength in [0, 1] */
+    int active;                /* 0: the slot is left alone */
+} lcm_variation_desc;
+#define LCM_VARIATION_MAX_BATCH 8
+int lcm_noise_variation_f32(void* lat0, int B, int h, int w, const lcm_variation_desc* descs, void* stream);
+
 /* ---- Lanczos resampler: fitting an upload to the request's size (csrc/resize.hip, csrc/resize.cpp) ----
  * The text below DEFINES the fitted picture bit for bit.  It is PIL's ImagingResample for 8-bit pixels with the Lanczos filter:
  * Image.resize((out_w, out_h), Image.LANCZOS) of an "L" or "RGB" picture gives the same bytes (verified against Pillow 12.2.0 by

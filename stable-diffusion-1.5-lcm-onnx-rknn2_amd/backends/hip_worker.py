@@ -33,7 +33,7 @@ import numpy as np
 import torch
 
 from ..lib import LcmHipError
-from ..pipeline import LcmHipPipeline, draw_noise, draw_noise_hires, draw_noise_img2img
+from ..pipeline import LcmHipPipeline, draw_noise, draw_noise_hires, draw_noise_img2img, draw_variation_sources
 from ..prompt import HipPromptEncoder
 from ..scheduler import LCMSchedule
 from .. import weights as _weights
@@ -44,6 +44,7 @@ from . import img2img as _img2img
 from . import inpaint as _inpaint
 from . import prompt_syntax as _prompt
 from . import refine as _refine
+from . import variation as _variation
 
 
 def parse_size(size) -> Tuple[int, int]:
@@ -338,7 +339,7 @@ class _Engine:
         self._stats_lock = threading.Lock()
         self.stats = dict(unet_evals=0, refine_cache_hits=0, refine_cache_misses=0, refine_cache_puts=0, controlnet_evals=0,
                           hires_requests=0, img2img_requests=0, inpaint_requests=0, controlnet_preprocessed=0,
-                          resized_on_device=0, prompt_chunks=0, weighted_prompts=0)
+                          resized_on_device=0, prompt_chunks=0, weighted_prompts=0, variation_requests=0)
         # ControlNet: where it comes from (CONTROLNET=<dir or file> | "synthetic" | None); loaded on the first request that
         # carries a hint, released with the pipeline
         self.controlnet_src = None
@@ -448,12 +449,16 @@ class _Engine:
                 t1 = _t.perf_counter()
                 noises = [it[2] for it in items] if all(len(it) > 2 and it[2] is not None for it in items) else None
                 seeds = [it[1] for it in items]
+                # variation seeds / seed-resize are per image, like the prompt: items that carry one (VariedItem, _with_variation)
+                # share the pass with plain ones, and a pass without any gets no variation= at all
+                varied = [getattr(it, "variation", None) for it in items]
+                var_kw = (lambda idx: dict(variation=[varied[i] for i in idx])) if any(v is not None for v in varied) else (lambda idx: {})
                 if _hires.is_hires_key(key):         # key = plain key + (KEY_TAG, target width, target height, hr_steps, strength, mode)
                     tw, th, hr_steps, strength, mode = key[7:12]
                     cap = pipe.hires_batch_cap(tw, th, hr_steps, strength, g, lane=lane, sizes=self.batch_sizes, n_ctx=n_ctx)
                     res = self._run_capped(items, noises, pe, kw, cap, stream, "hires_requests", lambda idx, sub_pe, sub_noises, sub_kw:
                                            pipe.generate(sub_pe, [seeds[i] for i in idx], width, height, steps, g, noises=sub_noises,
-                                                         lane=lane, hires=(tw, th, hr_steps, strength, mode), **sub_kw))
+                                                         lane=lane, hires=(tw, th, hr_steps, strength, mode), **var_kw(idx), **sub_kw))
                 elif _img2img.is_img2img_key(key):   # key = plain key + (KEY_TAG, strength); items carry the fitted picture
                     cap = pipe.img2img_batch_cap(width, height, steps, key[7], g, lane=lane, sizes=self.batch_sizes, n_ctx=n_ctx)
                     res = self._run_capped(items, noises, pe, kw, cap, stream, "img2img_requests", lambda idx, sub_pe, sub_noises, sub_kw:
@@ -466,7 +471,7 @@ class _Engine:
                                                                  _fit.stack([items[i][4] for i in idx]), width, height, steps, key[7],
                                                                  key[8], g, noises=sub_noises, lane=lane, **sub_kw))
                 elif len(key) > 6 and not _controlnet.is_control_key(key):
-                    res = self._run_refine(pipe, key, items, noises, pe, kw, lane, stream)
+                    res = self._run_refine(pipe, key, items, noises, pe, kw, lane, stream, var_kw)
                 else:                                # plain, or ControlNet: the hints ride along, the scale is key[7]
                     control = _controlnet.is_control_key(key)
                     pre = _controlnet.key_preprocessor(key) if control else ()
@@ -474,7 +479,7 @@ class _Engine:
                         kw = dict(kw, control=(_fit.stack([it[3] for it in items]), key[7]))
                         if pre:                          # a photo: the edge map is made on the device, ahead of the hint stack
                             kw["preprocess"] = pre
-                    out = pipe.generate(pe, seeds, width, height, steps, g, noises=noises, lane=lane, **kw)
+                    out = pipe.generate(pe, seeds, width, height, steps, g, noises=noises, lane=lane, **var_kw(range(len(items))), **kw)
                     res = _take([None] * len(items), out, range(len(items)))
                     with self._stats_lock:
                         self.stats["unet_evals"] += steps
@@ -486,6 +491,10 @@ class _Engine:
                 if fitted:
                     with self._stats_lock:
                         self.stats["resized_on_device"] += fitted
+                n_varied = len({id(it) for it, v in zip(items, varied) if v is not None})
+                if n_varied:
+                    with self._stats_lock:
+                        self.stats["variation_requests"] += n_varied
             finally:
                 self._leave_style()
         t2 = _t.perf_counter()
@@ -493,7 +502,7 @@ class _Engine:
             self.timing.append((len(items), t1 - t0, t2 - t1, t2))
         return res
 
-    def _run_refine(self, pipe, key, items, noises, pe, kw, lane, stream):
+    def _run_refine(self, pipe, key, items, noises, pe, kw, lane, stream, var_kw=lambda idx: {}):
         """The passes of a refinement batch (key = plain key + (d, p)).  Every item starts from its deepest cached x^k, k < p;
         items of one sampler pass must share that depth, so the batch is split by it (and each part cut to the plan batch
         sizes).  Every x^k a pass produces goes into the cache.  The bytes never depend on where a chain started: the draws of
@@ -501,7 +510,8 @@ class _Engine:
         width, height, steps, g = key[:4]
         d, p = key[6], key[7]
         cache = self.refine_cache
-        idents = [_refine.request_ident(it[0], key, it[1]) for it in items]
+        # (a varied request's x^k are its own: the resolved variation is part of the identity)
+        idents = [_refine.request_ident(it[0], key, it[1], getattr(it, "ident", None)) for it in items]
         found = [cache.deepest(idn, d, p) if cache.cap > 0 else (None, None) for idn in idents]
         res = [None] * len(items)
         for k0, idx in _refine.group_by_start([f[0] for f in found], self.batch_sizes):
@@ -510,7 +520,7 @@ class _Engine:
             start = None if k0 is None else (k0, [found[i][1] for i in idx])
             out = pipe.generate(sub_pe, [items[i][1] for i in idx], width, height, steps, g,
                                 noises=[noises[i] for i in idx] if noises is not None else None, lane=lane,
-                                strength=d, passes=p, start=start, **sub_kw)
+                                strength=d, passes=p, start=start, **var_kw(idx), **sub_kw)
             puts = 0
             if cache.cap > 0:
                 first = out["xk_first"]
@@ -877,6 +887,10 @@ class HipLcmWorker:
         inp = _inpaint.parse_inpaint(req)            # a mask without a picture raises here
         if i2i is not None:
             _fit.parse_resize_mode(req)              # its own error, for its own job; no part of the key (the picture is per image)
+        # variation seeds / seed-resize (backends/variation.py): their own errors, for their own job; no part of the key -- the
+        # variation is per image, plain and varied requests share passes
+        if _variation.parse_variation(req, width, height) is not None and (i2i is not None or inp is not None):
+            raise RuntimeError(_variation.NOT_COMBINED)
         if inp is not None:
             # inpaint jobs coalesce among themselves, never with image-to-image jobs: the plain key + strength and mask blur
             if hr is not None:
@@ -936,6 +950,28 @@ class HipLcmWorker:
         return all(v % 8 == 0 and v > 0 for v in key[:2] + more) and key[2] >= 1
 
     def _prepare(self, req, key):
+        """-> the request's item for ``run_batch``: ``_prepare_kind``'s tuple, as it is for every request without an active
+        variation; with one, the same tuple as a ``variation.VariedItem`` that also carries the variation's draws."""
+        return self._with_variation(self._prepare_kind(req, key), key)
+
+    def _with_variation(self, item, key):
+        """Variation seeds / seed-resize of the item's request (backends/variation.py): the subseed is resolved (a random one by
+        the seed's own policy when none or -1 was sent; it is not reported: ``run_job`` has no place for it) and the variation's
+        tensors are drawn HERE, on the caller's thread, from generators of their own (pipeline.py's RNG contract).  The
+        request's own draws are untouched."""
+        req, seed = item[0], item[1]
+        var = _variation.parse_variation(req, key[0], key[1])
+        if var is None:
+            return item
+        sub, t, hs, ws = var                         # (never on the SDXL worker: its _job_key has refused the request)
+        resized = (hs, ws) != (key[1] // 8, key[0] // 8)
+        subseed = _variation.resolve_subseed(sub) if t > 0.0 else None
+        if not self._drawable(key):                  # left to the pipeline's own size error
+            return item
+        s, base = draw_variation_sources(seed, subseed, hs, ws, self._engine.pipe.sched.init_noise_sigma, resized=resized)
+        return _variation.attach(item, (t, s, base), (subseed, t, hs, ws))
+
+    def _prepare_kind(self, req, key):
         """-> (req, seed, noise[, hint | picture[, mask]]): the seed policy of cuda_worker.py:210-213 and the request's RNG stream.
         An upload that does not have the request's size is fitted here on the host (LCM_RESIZE=pil, or outside the device path's
         domain) or handed on at its own size as a ``fit.Pending`` for the lane's stream to fit (backends/fit.py)."""
@@ -1174,7 +1210,8 @@ class HipLcmWorker:
             while idx:
                 n = max(s for s in sizes if s <= len(idx))
                 part, idx = idx[:n], idx[n:]
-                for i, (rgb, _) in zip(part, self._engine.run_batch(key, [(jobs[i].req, seeds[i]) for i in part])):
+                items = [self._with_variation((jobs[i].req, seeds[i]), key) for i in part]
+                for i, (rgb, _) in zip(part, self._engine.run_batch(key, items)):
                     rgbs[i] = rgb
         with ThreadPoolExecutor(max_workers=min(8, max(1, len(jobs)))) as ex:
             pngs = list(ex.map(encode_png, rgbs))
@@ -1210,6 +1247,8 @@ class HipLcmSDXLWorker(HipLcmWorker):
             raise RuntimeError("init_image: image-to-image is not served by the SDXL worker (SD1.5 and SD 2.x only)")
         if getattr(req, "mask", None) is not None or getattr(req, "mask_image", None) is not None:
             raise RuntimeError("mask: inpainting is not served by the SDXL worker (SD1.5 and SD 2.x only)")
+        if _variation.parse_variation(req, *parse_size(req.size)) is not None:
+            raise RuntimeError(_variation.SDXL_ERROR)
         return HipLcmWorker._kind_key(req)           # prompts are truncated to 77 tokens here, as ever: no ("ctx", n)
 
     def _synthetic_weights(self):

@@ -139,13 +139,16 @@ class RefineCache:
         return None, None
 
 
-def request_ident(req, key, seed):
-    """What x^k of a request depends on besides (d, k): prompt, seed, size, steps, guidance, style, level."""
+def request_ident(req, key, seed, variation=None):
+    """What x^k of a request depends on besides (d, k): prompt, seed, size, steps, guidance, style, level -- and, for a request
+    with an active variation (backends/variation.py), the resolved (subseed, strength, hs, ws) its initial latents were blended
+    with: without it pass 2 of a varied request would start from the unvaried request's cached x^1."""
     # (a negative prompt or a clip_skip other than 1 changes x^k too; requests without them keep the identity of always)
     ov = getattr(req, "override_settings", None)
     more = (getattr(req, "negative_prompt", None) or "", getattr(req, "clip_skip", None) or 1,
             (ov.get("CLIP_stop_at_last_layers") if isinstance(ov, dict) else None) or 1)
-    return (req.prompt, int(seed)) + tuple(key[:6]) + (more if more != ("", 1, 1) else ())
+    ident = (req.prompt, int(seed)) + tuple(key[:6]) + (more if more != ("", 1, 1) else ())
+    return ident if variation is None else ident + (("variation",) + tuple(variation),)
 
 
 def group_by_start(starts, sizes):

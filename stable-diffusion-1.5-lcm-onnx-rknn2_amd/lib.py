@@ -30,6 +30,14 @@ def build(verbose: bool = False) -> str:
 
 _vp, _i, _f, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
 
+
+class VariationDesc(C.Structure):
+    """lcm_variation_desc (include/lcm_hip.h): one request's slot of an lcm_noise_variation_f32 launch."""
+    _fields_ = [("low", _vp), ("high", _vp), ("hs", _i), ("ws", _i), ("t", _f), ("active", _i)]
+
+
+VARIATION_MAX_BATCH = 8    # LCM_VARIATION_MAX_BATCH
+
 _SIGS = {
     "lcm_gemm_f16": [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _i,
                      _i64, _i64, _i64, _i, _vp, _i64, C.POINTER(_i), _vp],
@@ -71,6 +79,7 @@ _SIGS = {
     "lcm_canny_link": [_vp, _vp, _vp, C.c_longlong, _i, _i, _i, _vp],
     "lcm_canny_rgb8": [_vp, _vp, _vp, C.c_longlong, _i, _i, _i, _f, _f, _vp],
     "lcm_invert_u8": [_vp, _vp, C.c_longlong, _vp],
+    "lcm_noise_variation_f32": [_vp, _i, _i, _i, C.POINTER(VariationDesc), _vp],
     "lcm_resize_lanczos_u8": [_vp, C.c_longlong, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_longlong, _vp, C.c_longlong, _vp],
     "lcm_resize_tables": [_i, _i, _i, _i, _vp, C.c_longlong],
     "lcm_resize_plan_tables": [_i] * 8 + [_vp, C.c_longlong],

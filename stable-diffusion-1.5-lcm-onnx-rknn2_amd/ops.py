@@ -633,6 +633,23 @@ def invert_u8(x, out):
     return out
 
 
+def noise_variation(lat0, B, h, w, descs):
+    """The variation blend and seed-resize paste of a batch's initial latents, one launch (lcm_noise_variation_f32,
+    include/lcm_hip.h): lat0 fp32 [B,4,h,w]; descs: per slot None (left alone) or (low, high, hs, ws, t) -- low / high fp32 device
+    tensors [4,hs,ws] (low None: the slot itself, a blend in place; high None with t == 0: low is pasted), t the strength."""
+    L = _lib.load()
+    if len(descs) != int(B):
+        raise ValueError(f"noise_variation: {len(descs)} descriptors for a batch of {B}")
+    arr = (_lib.VariationDesc * max(int(B), 1))()
+    for b, d in enumerate(descs):
+        if d is None:
+            continue
+        low, high, hs, ws, t = d
+        arr[b] = _lib.VariationDesc(_p(lat0[b]) if low is None else _p(low), _p(high), int(hs), int(ws), float(t), 1)
+    _lib.check(L.lcm_noise_variation_f32(_p(lat0), int(B), int(h), int(w), arr, _stream()), "lcm_noise_variation_f32")
+    return lat0
+
+
 def _resize_geometry(src, out_w, out_h, window):
     if src.dtype != torch.uint8 or src.dim() not in (2, 3) or (src.dim() == 3 and src.shape[2] not in (1, 3)):
         raise _lib.LcmHipError(f"resize: the source must be uint8 [H,W], [H,W,1] or [H,W,3], got {src.dtype} {tuple(src.shape)}")

@@ -13,6 +13,13 @@ A hires request (``generate(..., hires=)``) keeps that one generator: it draws t
 latents[1,4,h,w], then steps - 1 step noises -- and then, at the target shape, the re-noise tensor [1,4,H2/8,W2/8] and
 hr_steps - 1 step noises (``draw_noise_hires``).  Its bytes therefore depend only on (prompt, seed, size, steps, guidance, style,
 target size, hr_steps, strength, mode) -- not on the batch, the lane or what ran before.
+
+A variation (``generate(..., variation=)``; backends/variation.py) leaves that generator alone: G(seed) draws, exactly as above, the
+target-shape tensor x [1,4,h,w] and then the step noises.  The variation adds generators of its own (``draw_variation``):
+sub = randn(G'(subseed), [1,4,hs,ws]) and, only when a seed-resize is active, base = randn(G''(seed), [1,4,hs,ws]) -- a fresh
+generator seeded with the request's seed; otherwise base is x itself and (hs, ws) = (h, w).  Both are multiplied by
+init_noise_sigma like x.  lcm_noise_variation_f32 blends sub into base and pastes the result into x on the lane's stream, ahead of
+the captured pass; step noises are never blended.  These draws, too, happen on the host before anything is launched.
 """
 from __future__ import annotations
 
@@ -84,6 +91,30 @@ def draw_noise_img2img(seed: int, h: int, w: int, steps: int, sigma: float = 1.0
     return e0, rest
 
 
+def draw_variation_sources(seed: int, subseed: int, hs: int, ws: int, sigma: float = 1.0, resized: bool = False):
+    """The tensors a variation adds to a request's draws (module docstring), each from a generator of its own ->
+    (sub, base | None): sub = randn(G'(subseed), [1,4,hs,ws]) sigma; base = randn(G''(seed), [1,4,hs,ws]) sigma when a seed-resize
+    is active (``resized``), else None: the request's own initial latents are the base.  subseed None (strength 0, a seed-resize
+    alone): sub is None, nothing is drawn for it."""
+    sub = base = None
+    if subseed is not None:
+        (sub,), = _draw(subseed, (hs, ws, 1))
+        sub = sub * sigma
+    if resized:
+        (base,), = _draw(seed, (hs, ws, 1))
+        base = base * sigma
+    return sub, base
+
+
+def draw_variation(seed: int, subseed: int, h: int, w: int, hs: int, ws: int, sigma: float = 1.0, n_extra: int = 0):
+    """A request with a variation, all of its draws -> (x, step noises, sub, base | None): x and the ``n_extra`` step noises are
+    ``draw_noise(seed, h, w, n_extra, sigma)`` bit for bit (the request's generator is not touched by the variation); sub and base
+    are ``draw_variation_sources`` at the source shape (hs, ws), base only when that shape is not (h, w)."""
+    x, extra = draw_noise(seed, h, w, n_extra, sigma)
+    sub, base = draw_variation_sources(seed, subseed, hs, ws, sigma, resized=(int(hs), int(ws)) != (int(h), int(w)))
+    return x, extra, sub, base
+
+
 MAX_MASK_BLUR = 32.0
 
 
@@ -144,6 +175,7 @@ class _Lane:
         self.fit_src = self.fit_ws = None      # uploads of another size (backends/fit.py): the raw picture and the resampler's workspace
         self.pre_ws = None            # ControlNet preprocessor (generate(preprocess=)): the Canny workspace, sized on first use
         self.enc_plans = {}           # (B, H, W) -> _EncPlan: the encoder stage of image-to-image requests
+        self.var_h = self.var_d = None         # variations (generate(variation=)): pinned / device staging of sub and base, sized on first use
 
 
 class _Plan:
@@ -509,6 +541,8 @@ class LcmHipPipeline:
             nsa, nsb = self.sched.renoise_coefficients(ts_cut[0])
             passes += [ts_cut] * run
         ni = 0                                        # next tensor of P.noise, in draw order
+        if taps is not None and not cached:
+            taps["latents0"] = P.lat0.cpu()           # the initial latents as the pass reads them (after a variation's blend)
         if cached:
             if P.kind not in P.FROM_STATE:            # hires stage 2: lcm_latents_upscale_renoise wrote P.lat (and P.xk[0])
                 ops.latents_renoise(P.xk[0], P.noise[0], nsa, nsb, P.lat, B, h, w, dup=P.do_cfg)
@@ -818,11 +852,13 @@ class LcmHipPipeline:
         else:
             P.graph.launch()
 
-    def _request(self, plans, pe, negative_embeds, guidance_scale, upload=None, front=None, want_float=False, taps=None, more=None):
+    def _request(self, plans, pe, negative_embeds, guidance_scale, upload=None, front=None, want_float=False, taps=None, more=None,
+                 vary=None):
         """The one sequence of every request kind, on the lane's stream.  plans: every plan of the request, the last one gives
         the picture; their pinned staging (h_lat, h_noise) is filled.  upload(): the kind's own uploads (hint, picture, start
-        latents, SDXL rows); front(eager): the stage ahead of the last plan and its hand-over launch; more(): device-side
-        copies to queue after the read-backs -> (base result dict, what more() returned).  The rules:
+        latents, SDXL rows); vary(): a variation's upload and its one launch into the first plan's lat0 (``_stage_variation``; None
+        for every request without one); front(eager): the stage ahead of the last plan and its hand-over launch; more():
+        device-side copies to queue after the read-backs -> (base result dict, what more() returned).  The rules:
           * noise is drawn on the host, by the caller, before anything is launched: the graphs are RNG-free;
           * the graphs of EVERY plan of the request are ensured before its uploads: a warm-up pass overwrites plan state;
           * eager launches (use_graph=False, want_float, taps) hold _build_lock: they allocate scratch;
@@ -842,6 +878,8 @@ class LcmHipPipeline:
                 self._upload_text(Q, pe, negative_embeds, guidance_scale)
             if upload is not None:
                 upload()
+            if vary is not None:
+                vary()
             if front is not None:
                 front(eager)
             self._run_plan(P, guidance_scale, eager, want_float, taps)
@@ -857,13 +895,13 @@ class LcmHipPipeline:
 
     @torch.inference_mode()
     def generate_hires(self, prompt_embeds, seeds, width, height, steps, hires, guidance_scale=1.0, negative_embeds=None,
-                       want_float=False, noises=None, lane=0):
+                       want_float=False, noises=None, lane=0, variation=None):
         """Hires fix: sample at (width, height) for ``steps`` steps, upscale the denoised latents to (W2, H2) with latent upscaler
         ``mode`` (lib.UPSCALE_MODES), re-noise them to the first timestep of ``timesteps(hr_steps, strength)``, run ``hr_steps``
         steps there and decode once.  hires = (W2, H2, hr_steps, strength, mode).  The front stage of the request (``_request``)
         is the "latents" plan at the base size (no VAE decode) and lcm_latents_upscale_renoise into the state of the
         "from-state" refinement plan at the target size.  noises: optional per-request
-        ``draw_noise_hires`` results.  Returns the usual dict at the target size plus ``lowres_latents`` (host fp32 [B,4,h,w],
+        ``draw_noise_hires`` results.  variation: as ``generate``'s, blended into the initial latents of the low-resolution stage.  Returns the usual dict at the target size plus ``lowres_latents`` (host fp32 [B,4,h,w],
         the plain request's final latents bit for bit) and ``unet_evals`` = steps + hr_steps (doubled under classifier-free
         guidance); with want_float (eager launches) also ``image`` and ``upscaled_latents`` (host fp32 [B,4,H2/8,W2/8])."""
         torch.cuda.set_device(self.device)
@@ -899,13 +937,14 @@ class LcmHipPipeline:
             for i, n in enumerate(hi):
                 P2.h_noise[i, b].copy_(n[0])
         low = P1.lat[B:] if do_cfg else P1.lat
+        vary = self._stage_variation(P1, variation, B, h, w)
 
         def front(eager):                                # stage 1 -> hand-over into stage 2's state
             self._run_plan(P1, guidance_scale, eager)
             ops.latents_upscale_renoise(low, h, w, P2.noise[0], nsa, nsb, mode, P2.lat, B, h2, w2, x_up=P2.xk[0], dup=do_cfg)
 
         out, _ = self._request([P1, P2], pe, negative_embeds, guidance_scale, front=front, want_float=want_float,
-                               more=lambda: P1.h_latout.copy_(low, non_blocking=True))
+                               more=lambda: P1.h_latout.copy_(low, non_blocking=True), vary=vary)
         out.update(lowres_latents=P1.h_latout.numpy().copy(), unet_evals=(steps + hr_steps) * (2 if do_cfg else 1))
         if want_float:
             out["upscaled_latents"] = P2.xk[0].cpu().numpy()
@@ -914,7 +953,7 @@ class LcmHipPipeline:
     @torch.inference_mode()
     def generate(self, prompt_embeds, seeds, width, height, steps, guidance_scale=1.0, negative_embeds=None,
                  want_float=False, taps=None, latents=None, added=None, negative_added=None, noises=None, lane=0,
-                 strength=None, passes=0, start=None, control=None, hires=None, preprocess=None):
+                 strength=None, passes=0, start=None, control=None, hires=None, preprocess=None, variation=None):
         """prompt_embeds: [B,77 n,ctx] (any float dtype, host or device; n chunks of a long prompt, concatenated: the
         plan, its graph and its cross-attention launches are those of n -- n = 1 is the plan of always); seeds: B ints.  noises: optional per-request
         ``draw_noise(seed, h, w, steps - 1, init_noise_sigma)`` results drawn ahead by the callers (the worker's pool
@@ -938,6 +977,13 @@ class LcmHipPipeline:
         the pass are those of a finished hint.  None / (): the hint is the finished map.  Needs control.
         hires = (W2, H2, hr_steps, strength, mode): hires fix -- ``generate_hires`` (its own RNG contract and result keys); not
         combined with passes, control, latents or SDXL conditioning.
+        variation: per request None | (t, sub, base | None) -- variation seeds and seed-resize (module docstring;
+        ``draw_variation``).  sub / base fp32 host tensors [1,4,hs,ws], already multiplied by init_noise_sigma; t the subseed strength
+        in [0, 1].  base None: the request's own initial latents are blended in place with sub ((hs, ws) = (h, w)); with a base the
+        blend happens at the source shape and is pasted, centred, into them (include/lcm_hip.h, variation seeds).  One launch of
+        lcm_noise_variation_f32 for the whole batch, on the lane's stream between the uploads and the captured pass; slots with
+        None are not touched, and a call without any variation queues nothing.  It is no part of the plan key.  A chain that
+        starts from cached latents (start=) never reads the initial latents, so nothing is launched there.
         Returns dict(rgb uint8 [B,H,W,3] (host), latents fp32 [B,4,h,w] (host), pool8 fp16 [B,4,8,8] (host))."""
         torch.cuda.set_device(self.device)        # the pool may call from a thread other than the constructing one
         if hires is not None:
@@ -949,7 +995,7 @@ class LcmHipPipeline:
                 raise LcmHipError("hires fix draws its noise from the seeds and is not served for SDXL: latents= / added= / taps= "
                                   "are not supported")
             return self.generate_hires(prompt_embeds, seeds, width, height, steps, hires, guidance_scale, negative_embeds,
-                                       want_float=want_float, noises=noises, lane=lane)
+                                       want_float=want_float, noises=noises, lane=lane, variation=variation)
         pe = torch.as_tensor(prompt_embeds)
         B = pe.shape[0]
         check_size(width, height)
@@ -1007,6 +1053,11 @@ class LcmHipPipeline:
                     P.h_noise[i, b].copy_(n[0])
             if hint is not None:
                 self._stage(P.h_hint, hint)
+        vary = None
+        if variation is not None and not (refine is not None and refine[2]):
+            if self.unet.has_added:
+                raise LcmHipError("variation seeds are not served for SDXL-family UNets")
+            vary = self._stage_variation(P, variation, B, h, w)
 
         def upload():
             if hint is not None:
@@ -1021,7 +1072,7 @@ class LcmHipPipeline:
                 self._upload_added(P, added, negative_added)
 
         out, xk = self._request([P], pe, negative_embeds, guidance_scale, upload, want_float=want_float, taps=taps,
-                                more=(lambda: P.xk.clone()) if refine is not None else None)
+                                more=(lambda: P.xk.clone()) if refine is not None else None, vary=vary)
         if refine is not None:
             out["xk"], out["xk_first"] = xk, passes - refine[1]
             out["unet_evals"] = steps * (refine[1] + (0 if refine[2] else 1))
@@ -1097,6 +1148,67 @@ class LcmHipPipeline:
             if L.fit_ws is None or L.fit_ws.numel() < need:
                 L.fit_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             ops.resize_lanczos_u8(src, dst[b], L.fit_ws, f.fit_w, f.fit_h, win)
+
+    def _stage_variation(self, P: _Plan, variation, B, h, w):
+        """The variations of a batch (``generate``'s variation=) -> None when no slot has one, else vary(): called on the lane's
+        stream after the uploads, it copies the staged sub / base tensors to the device and queues the one launch of
+        lcm_noise_variation_f32 into P.lat0.  Here, on the caller's side and before anything is launched, the tensors are checked
+        and copied into the lane's pinned staging.  Pinned and device staging belong to the lane, are sized on first use and grow
+        on demand (a lane that never sees a variation owns neither); the device side is allocated on the lane's stream, which
+        orders every reuse behind the launch that read it.  Nothing is read back."""
+        if variation is None:
+            return None
+        if len(variation) != B:
+            raise LcmHipError(f"variation: {len(variation)} entries for a batch of {B}")
+        slots, n = [], 0                                 # per slot None | (t, hs, ws, offset of sub | None, offset of base | None)
+        srcs = []
+        for b, v in enumerate(variation):
+            if v is None:
+                slots.append(None)
+                continue
+            t, sub, base = v
+            t = float(t)
+            if not 0.0 <= t <= 1.0:                      # NaN fails both comparisons
+                raise LcmHipError(f"request {b}: variation strength {t} outside [0, 1]")
+            if t > 0.0 and sub is None:
+                raise LcmHipError(f"request {b}: a variation of strength {t} needs the subseed's noise")
+            if t == 0.0 and base is None:                # nothing to blend, nothing to paste: the plain request
+                slots.append(None)
+                continue
+            ts = [None if x is None else torch.as_tensor(x, dtype=torch.float32).reshape(-1, *torch.as_tensor(x).shape[-2:])
+                  for x in ((sub if t > 0.0 else None), base)]
+            shape = next(x.shape for x in ts if x is not None)
+            hs, ws = int(shape[1]), int(shape[2])
+            if any(x is not None and tuple(x.shape) != (4, hs, ws) for x in ts) or not (1 <= hs <= 256 and 1 <= ws <= 256):
+                raise LcmHipError(f"request {b}: variation noise must be fp32 [1,4,hs,ws] with sides in 1..256, got "
+                                  f"{[None if x is None else tuple(x.shape) for x in ts]}")
+            if base is None and (hs, ws) != (h, w):
+                raise LcmHipError(f"request {b}: a variation without a seed-resize base blends in place and needs noise of the "
+                                  f"request's latent shape {h}x{w}, got {hs}x{ws}")
+            offs = []
+            for x in ts:
+                offs.append(None if x is None else n)
+                if x is not None:
+                    srcs.append((n, x))
+                    n += x.numel()
+            slots.append((t, hs, ws, offs[0], offs[1]))
+        if n == 0:
+            return None
+        L = P.lane
+        if L.var_h is None or L.var_h.numel() < n:
+            L.var_h = torch.empty(n, dtype=torch.float32).pin_memory()
+        for o, x in srcs:
+            L.var_h[o:o + x.numel()].copy_(x.reshape(-1))
+
+        def vary():
+            if L.var_d is None or L.var_d.numel() < n:
+                L.var_d = torch.empty(L.var_h.numel(), dtype=torch.float32, device=self.device)
+            L.var_d[:n].copy_(L.var_h[:n], non_blocking=True)
+            view = lambda o, hs, ws: None if o is None else L.var_d[o:o + 4 * hs * ws]
+            # low: the seed-resize base, or None -- the slot itself, blended in place
+            ops.noise_variation(P.lat0, B, h, w, [None if s is None else (view(s[4], s[1], s[2]), view(s[3], s[1], s[2]), s[1], s[2], s[0])
+                                                  for s in slots])
+        return vary
 
     def _preprocess_hint(self, P: _Plan, pre, B, H, W):
         """The photo in P.hint (uploaded, and fitted where it came at another size) -> the map in P.hint, on the current (the
