@@ -372,6 +372,43 @@ int lcm_scheduler_step_handover(const void* eps, const void* eps_uncond, float g
                                 const float* coef6, float next_sqrt_a, float next_sqrt_b, int prediction_type, int B, int h, int w,
                                 int dup, void* stream);
 
+/* ---- samplers: Euler, Euler a, DDIM and DPM++ 2M as one step launch (csrc/sampler.hip, samplers.py) ----
+ * Definitions.  abar[t] = alphas_cumprod[t], sigma[t] = sqrt((1 - abar[t]) / abar[t]) for t = 0..999.  For a noise level s:
+ * sa(s) = 1 / sqrt(1 + s^2), sb(s) = s sa(s).  The sampler state is the variance-preserving one the UNet reads (with k-diffusion's
+ * state X, x = sa(s) X): nothing scales the UNet's input.
+ *   t_to_sigma(t), fractional t: linear in log sigma between floor(t) and ceil(t).  sigma_to_t(s): the inverse on the same table,
+ *   the weight clipped to [0, 1].
+ *   Schedules of n steps, both with s_n = 0 appended:  "normal"  s_i = t_to_sigma(t_i), t_i = linspace(999, 0, n), the UNet is
+ *   evaluated at the fractional t_i;  "karras"  s_i = (smax^(1/7) + i/(n-1) (smin^(1/7) - smax^(1/7)))^7 with smax = sigma[999],
+ *   smin = sigma[0] (n = 1: smax), the UNet is evaluated at t_i = sigma_to_t(s_i).
+ *   Every step is x' = cx x + c0 x0 + c1 x0_prev + cn noise, then x0_prev <- x0, with m the model output after guidance and x0
+ *   from m by the prediction type as lcm_scheduler_step_ex states it (sqrt_alpha_t = sa, sqrt_beta_t = sb).  With s = s_i,
+ *   s' = s_(i+1), S = sa:
+ *     Euler     cx = S(s') s' / (S(s) s), c0 = S(s') (1 - s'/s).
+ *     Euler a   sup = min(s', sqrt(s'^2 (s^2 - s'^2) / s^2)), sdn = sqrt(s'^2 - sup^2): Euler towards sdn scaled by S(s'),
+ *               cx = S(s') sdn / (S(s) s), c0 = S(s') (1 - sdn/s), cn = S(s') sup; the last step (s' = 0) is x' = x0, no noise.
+ *     DPM++ 2M  h = ln s - ln s', e = -expm1(-h), cx = S(s') s' / (S(s) s); first step c0 = S(s') e; later steps with
+ *               r = h_prev / h: c0 = S(s') e (1 + 1/(2r)), c1 = -S(s') e / (2r); the last step (s' = 0) is x' = x0.
+ *     DDIM      diffusers' DDIMScheduler, eta 0, "leading" spacing, steps_offset 1: integer t_i = (n-1-i) (1000 / n) + 1,
+ *               prev = t_i - 1000 / n (integer division; prev < 0 uses final_alpha_cumprod); cx = sb_prev / sb_t,
+ *               c0 = sa_prev - sb_prev sa_t / sb_t.
+ *   Initial state: x = noise sb(s_0) for Euler, Euler a and DPM++ 2M, x = noise for DDIM.
+ *   These are written after the published formulas of k-diffusion, A1111 and diffusers; none of them was at hand to compare
+ *   with, so equality with any of them is unverified.
+ * lcm_sampler_step: eps / eps_uncond fp32 NHWC [B,h,w,4] (16-byte aligned; eps_uncond NULL: no guidance); lat fp32 NCHW
+ * [B,4,h,w], updated in place; x0_prev fp32 NCHW [B,4,h,w], read only when c1 != 0 and always written; noise fp32 NCHW, read
+ * only when cn != 0 (cn != 0 with noise NULL is LCM_EINVAL).  dup != 0: lat points at the second half of a [2B,4,h,w] state and
+ * the first half receives the same values (as lcm_scheduler_step_handover).  Operation order per element, every operation
+ * rounded to fp32 once (rn):
+ *   m  = eps_uncond ? fma(guidance, eps - eps_uncond, eps_uncond) : eps
+ *   x0 = epsilon: fma(-sb, m, x) / sa;  v: fma(-sb, m, sa * x);  sample: m
+ *   r  = fma(cx, x, c0 * x0);  c1 != 0: r = fma(c1, x0_prev, r);  cn != 0: r = fma(cn, noise, r)
+ * An element reads its own operands only: a request's bits depend neither on the batch size nor on its position.  A null or
+ * misaligned pointer, a bad shape (B*4*h*w < 2^30) or an unknown prediction type returns LCM_EINVAL before anything is enqueued. */
+int lcm_sampler_step(const void* eps, const void* eps_uncond, float guidance, void* lat, void* x0_prev, const void* noise, float sa,
+                     float sb, float cx, float c0, float c1, float cn, int prediction_type, int B, int h, int w, int dup,
+                     void* stream);
+
 /* ---- hires fix: the hand-over between two sizes ----
  * lat_out = fmaf(sqrt_b, noise, sqrt_a * up(x0)) in one launch: x0 fp32 NCHW [B,4,h,w] (the denoised latents of the
  * low-resolution pass) is upscaled to [B,4,H,W] with one of A1111's latent upscalers and re-noised like lcm_latents_renoise.

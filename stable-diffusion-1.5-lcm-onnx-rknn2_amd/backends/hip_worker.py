@@ -16,6 +16,8 @@ Env (as the reference, backends/cuda_worker.py:43-61):
                              engine; default 64, 0 turns it off
   LCM_RESIZE                 hip (default) | pil: where an upload of another size than the request's is fitted -- the HIP Lanczos
                              resampler on the lane's stream, or PIL on the caller's thread; the bytes are the same (backends/fit.py)
+  LCM_SAMPLERS               request (default) | lcm: whether ``sampler_name`` / ``scheduler`` are read (backends/sampler.py); with lcm
+                             every request is stepped by the LCM sampler, as before the fields were known
   CUDA_DTYPE                 fp16 (default).  bf16 / fp32 -- which the reference honours -- are REFUSED unless LCM_HIP_DTYPE=fp16
                              says to run them in this backend's one arithmetic (fp16 operands, fp32 accumulation)
 """
@@ -44,6 +46,7 @@ from . import img2img as _img2img
 from . import inpaint as _inpaint
 from . import prompt_syntax as _prompt
 from . import refine as _refine
+from . import sampler as _sampler
 from . import variation as _variation
 
 
@@ -278,6 +281,14 @@ def resize(img, width, height, mode=0) -> np.ndarray:
     return host.numpy()
 
 
+def samplers():
+    """What ``/sdapi/v1/samplers`` answers: [{"name", "aliases", "options"}], LCM first (the reference answers LCM alone,
+    server/compat_endpoints.py:132-135), then the names ``sampler_name`` serves.  With LCM_SAMPLERS=lcm: LCM alone."""
+    from .. import samplers as _s
+    full = _s.sampler_list()
+    return full if _sampler.mode() == "request" else full[:1]
+
+
 def _rows(x, idx, n):
     """The per-request conditioning rows ``idx`` of a batch of n: tensors with n leading rows are gathered, tuples (SDXL's
     ``added``) and dicts walked, anything else passed through; the whole batch in order is returned as it is."""
@@ -339,7 +350,7 @@ class _Engine:
         self._stats_lock = threading.Lock()
         self.stats = dict(unet_evals=0, refine_cache_hits=0, refine_cache_misses=0, refine_cache_puts=0, controlnet_evals=0,
                           hires_requests=0, img2img_requests=0, inpaint_requests=0, controlnet_preprocessed=0,
-                          resized_on_device=0, prompt_chunks=0, weighted_prompts=0, variation_requests=0)
+                          resized_on_device=0, prompt_chunks=0, weighted_prompts=0, variation_requests=0, sampler_requests=0)
         # ControlNet: where it comes from (CONTROLNET=<dir or file> | "synthetic" | None); loaded on the first request that
         # carries a hint, released with the pipeline
         self.controlnet_src = None
@@ -432,6 +443,8 @@ class _Engine:
         """One batched sampler pass for ``items`` = [(req, seed[, noise])], all of ``key``, on lane ``lane``;
         -> per-item (rgb, pool8 row)."""
         key, n_ctx = _prompt.split_ctx(key)          # a long-prompt pass: the kind's own key + ("ctx", n)
+        key, smp = _sampler.split_key(key)           # a sampler pass: the kind's own key + ("sampler", name, sigmas); None: LCM
+        smp_kw = dict(sampler=smp) if smp is not None else {}
         width, height, steps, g, style_id, level = key[:6]
         import time as _t
         t0 = _t.perf_counter()
@@ -460,10 +473,11 @@ class _Engine:
                                            pipe.generate(sub_pe, [seeds[i] for i in idx], width, height, steps, g, noises=sub_noises,
                                                          lane=lane, hires=(tw, th, hr_steps, strength, mode), **var_kw(idx), **sub_kw))
                 elif _img2img.is_img2img_key(key):   # key = plain key + (KEY_TAG, strength); items carry the fitted picture
-                    cap = pipe.img2img_batch_cap(width, height, steps, key[7], g, lane=lane, sizes=self.batch_sizes, n_ctx=n_ctx)
+                    cap = pipe.img2img_batch_cap(width, height, steps, key[7], g, lane=lane, sizes=self.batch_sizes, n_ctx=n_ctx, **smp_kw)
                     res = self._run_capped(items, noises, pe, kw, cap, stream, "img2img_requests", lambda idx, sub_pe, sub_noises, sub_kw:
                                            pipe.generate_img2img(sub_pe, [seeds[i] for i in idx], _fit.stack([items[i][3] for i in idx]),
-                                                                 width, height, steps, key[7], g, noises=sub_noises, lane=lane, **sub_kw))
+                                                                 width, height, steps, key[7], g, noises=sub_noises, lane=lane, **smp_kw,
+                                                                 **sub_kw))
                 elif _inpaint.is_inpaint_key(key):   # key = plain key + (KEY_TAG, strength, mask_blur); items carry picture and mask
                     cap = pipe.inpaint_batch_cap(width, height, steps, key[7], g, lane=lane, sizes=self.batch_sizes, n_ctx=n_ctx)
                     res = self._run_capped(items, noises, pe, kw, cap, stream, "inpaint_requests", lambda idx, sub_pe, sub_noises, sub_kw:
@@ -479,7 +493,8 @@ class _Engine:
                         kw = dict(kw, control=(_fit.stack([it[3] for it in items]), key[7]))
                         if pre:                          # a photo: the edge map is made on the device, ahead of the hint stack
                             kw["preprocess"] = pre
-                    out = pipe.generate(pe, seeds, width, height, steps, g, noises=noises, lane=lane, **var_kw(range(len(items))), **kw)
+                    out = pipe.generate(pe, seeds, width, height, steps, g, noises=noises, lane=lane, **var_kw(range(len(items))), **smp_kw,
+                                        **kw)
                     res = _take([None] * len(items), out, range(len(items)))
                     with self._stats_lock:
                         self.stats["unet_evals"] += steps
@@ -491,6 +506,9 @@ class _Engine:
                 if fitted:
                     with self._stats_lock:
                         self.stats["resized_on_device"] += fitted
+                if smp is not None:
+                    with self._stats_lock:
+                        self.stats["sampler_requests"] += len({id(it) for it in items})
                 n_varied = len({id(it) for it, v in zip(items, varied) if v is not None})
                 if n_varied:
                     with self._stats_lock:
@@ -645,6 +663,7 @@ class HipLcmWorker:
                 raise RuntimeError("MODEL_ROOT is required for BACKEND=hip")
             if not model_name:
                 raise RuntimeError("MODEL is required for BACKEND=hip")
+        _sampler.mode()                              # LCM_SAMPLERS: its own error, before anything is loaded
         dtype_str = os.environ.get("CUDA_DTYPE", "fp16").lower().strip()
         if dtype_str not in ("fp16", "bf16", "fp32"):
             raise RuntimeError(f"Unknown CUDA_DTYPE={dtype_str}, expected fp16, bf16 or fp32")      # cuda_worker.py:55-61
@@ -862,6 +881,8 @@ class HipLcmWorker:
         (``enable_hr``, backends/hires.py) coalesce among themselves: the plain key + ("hires", target size, hr_steps, strength,
         mode).  Image-to-image requests (a picture, backends/img2img.py) get the plain key + ("img2img", strength); with a mask
         (backends/inpaint.py) they are inpaint requests with the plain key + ("inpaint", strength, mask_blur) instead.
+        A request with a served ``sampler_name`` (backends/sampler.py; plain, ControlNet and image-to-image requests) appends
+        ("sampler", canonical name, "karras" | "normal") to its kind's key: such jobs coalesce among themselves.
         A prompt of n > 1 chunks (backends/prompt_syntax.py; under classifier-free guidance the longer of prompt and negative
         prompt counts) appends ("ctx", n) to whichever of these keys the request has: the pass has 77 n context rows.  With n == 1 --
         weighted or not, with or without a negative prompt -- the key is the one of always; the texts and ``clip_skip`` are per
@@ -891,6 +912,15 @@ class HipLcmWorker:
         # variation is per image, plain and varied requests share passes
         if _variation.parse_variation(req, width, height) is not None and (i2i is not None or inp is not None):
             raise RuntimeError(_variation.NOT_COMBINED)
+        smp = _sampler.parse_sampler(req)            # None: the LCM sampler, the key of always
+        if smp is not None:
+            if inp is not None:
+                raise RuntimeError(_sampler.NOT_COMBINED + "mask")
+            if hr is not None:
+                raise RuntimeError(_sampler.NOT_COMBINED + "enable_hr")
+            if rf is not None:
+                raise RuntimeError(_sampler.NOT_COMBINED + "refinement (denoise_strength < 1 or pass_number > 1)")
+        tail = _sampler.tail(smp)
         if inp is not None:
             # inpaint jobs coalesce among themselves, never with image-to-image jobs: the plain key + strength and mask blur
             if hr is not None:
@@ -908,7 +938,7 @@ class HipLcmWorker:
                 raise RuntimeError("init_image is not combined with refinement (denoise_strength < 1 or pass_number > 1)")
             if ctl is not None:
                 raise RuntimeError("init_image is not combined with controlnet_image")
-            return key + (_img2img.KEY_TAG, i2i[0])
+            return key + (_img2img.KEY_TAG, i2i[0]) + tail
         if hr is not None:
             if rf is not None:
                 raise RuntimeError("enable_hr is not combined with refinement (denoise_strength < 1 or pass_number > 1)")
@@ -920,8 +950,8 @@ class HipLcmWorker:
             # with a preprocessor, its name and parameters: ("canny", lo, hi) / ("invert",)
             if rf is not None:
                 raise RuntimeError("controlnet_image is not combined with refinement (denoise_strength < 1 or pass_number > 1)")
-            return key + (_controlnet.KEY_TAG, ctl[0]) + _controlnet.parse_preprocessor(req)
-        return key if rf is None else key + rf
+            return key + (_controlnet.KEY_TAG, ctl[0]) + _controlnet.parse_preprocessor(req) + tail
+        return key + tail if rf is None else key + rf
 
     def _bind_prompt_ctx(self):
         """Give this worker's ``_job_key`` the engine's own chunk count: its tokenizer, its text encoder's depth (clip_skip is
@@ -977,6 +1007,7 @@ class HipLcmWorker:
         domain) or handed on at its own size as a ``fit.Pending`` for the lane's stream to fit (backends/fit.py)."""
         eng = self._engine
         key, _ = _prompt.split_ctx(key)              # the prompt's length changes nothing here
+        key, smp = _sampler.split_key(key)           # a sampler draws exactly what the LCM sampler draws for the request
         seed = int(req.seed) if getattr(req, "seed", None) is not None else int(torch.randint(0, 100_000_000, (1,)).item())
         # the request's RNG stream (initial latents, then one draw per remaining step) is drawn HERE, on the caller's
         # thread: pool threads do it in parallel and the GPU dispatcher's serial path shrinks by ~0.5 ms per request
@@ -992,7 +1023,10 @@ class HipLcmWorker:
                     _fit.prepare(pic, key[0], key[1], mode, _img2img.fit_init), _fit.prepare(mask, key[0], key[1], mode, _inpaint.fit_mask))
         if _img2img.is_img2img_key(key):             # encoder on first use, the schedule's own error, the picture, the draws
             eng.ensure_vae_encoder()
-            _refine.check_schedule(sched, steps, key[7])
+            if smp is None:
+                _refine.check_schedule(sched, steps, key[7])
+            else:                                    # the LCM-only step bound does not apply; DDIM with no timestep left raises here
+                _sampler.check_img2img(sched, smp, steps, key[7])
             pic = _fit.prepare(_img2img.parse_img2img(req)[1], key[0], key[1], _fit.parse_resize_mode(req), _img2img.fit_init)
             return (req, seed, draw_noise_img2img(seed, h8, w8, steps) if self._drawable(key) else None, pic)
         if _hires.is_hires_key(key):                 # the schedule's own error first, then the draws at both shapes
@@ -1249,6 +1283,8 @@ class HipLcmSDXLWorker(HipLcmWorker):
             raise RuntimeError("mask: inpainting is not served by the SDXL worker (SD1.5 and SD 2.x only)")
         if _variation.parse_variation(req, *parse_size(req.size)) is not None:
             raise RuntimeError(_variation.SDXL_ERROR)
+        if _sampler.parse_sampler(req) is not None:
+            raise RuntimeError(_sampler.SDXL_ERROR)
         return HipLcmWorker._kind_key(req)           # prompts are truncated to 77 tokens here, as ever: no ("ctx", n)
 
     def _synthetic_weights(self):

@@ -72,6 +72,7 @@ _SIGS = {
     "lcm_vae_enc_conv_in_u8": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lcm_vae_posterior_renoise": [_vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lcm_scheduler_step_handover": [_vp, _vp, _f, _vp, _vp, _vp, C.POINTER(C.c_float), _f, _f, _i, _i, _i, _i, _i, _vp],
+    "lcm_sampler_step": [_vp, _vp, _f, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _vp],
     "lcm_inpaint_mask_prepare": [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp],
     "lcm_scheduler_step_inpaint": [_vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_float), _i, _f, _f, _i, _i, _i, _i, _i, _vp],
     "lcm_inpaint_composite_rgb8": [_vp, _vp, _vp, _i, _i, _i, _vp],

@@ -547,6 +547,21 @@ def scheduler_step_handover(eps, lat, noise, xk, coef6, next_sqrt_a, next_sqrt_b
     return lat
 
 
+def sampler_step(eps, lat, x0_prev, noise, sa, sb, cx, c0, c1, cn, B, h, w, *, eps_uncond=None, guidance=1.0, pred="epsilon",
+                 dup=False):
+    """One step of Euler / Euler a / DDIM / DPM++ 2M in place on ``lat`` (include/lcm_hip.h, samplers):
+    lat <- cx lat + c0 x0 + c1 x0_prev + cn noise, x0_prev <- x0.  noise: None when cn == 0.  dup: ``lat`` is the second half of a
+    [2B,4,h,w] state; the first half is written too."""
+    if pred not in _lib.PREDICTION_TYPES:
+        raise ValueError(f"unknown prediction type {pred!r}: expected one of {sorted(_lib.PREDICTION_TYPES)}")
+    L = _lib.load()
+    rc = L.lcm_sampler_step(_p(eps), _p(eps_uncond), float(guidance), _p(lat), _p(x0_prev), _p(noise), float(sa), float(sb), float(cx),
+                            float(c0), float(c1), float(cn), _lib.PREDICTION_TYPES[pred], int(B), int(h), int(w), int(bool(dup)),
+                            _stream())
+    _lib.check(rc, "lcm_sampler_step")
+    return lat
+
+
 def _record_plain(replay):
     """A launch with nothing to tune, in the thread's record list (``recording``): counted and replayable, never timed."""
     RECORD = _record_list()

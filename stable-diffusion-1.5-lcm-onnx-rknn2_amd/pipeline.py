@@ -20,6 +20,10 @@ sub = randn(G'(subseed), [1,4,hs,ws]) and, only when a seed-resize is active, ba
 generator seeded with the request's seed; otherwise base is x itself and (hs, ws) = (h, w).  Both are multiplied by
 init_noise_sigma like x.  lcm_noise_variation_f32 blends sub into base and pastes the result into x on the lane's stream, ahead of
 the captured pass; step noises are never blended.  These draws, too, happen on the host before anything is launched.
+
+A request with a sampler (``generate(..., sampler=)``, ``generate_img2img(..., sampler=)``; samplers.py) draws exactly the tensors
+the same request draws without one.  Euler a reads the step noises, in draw order; Euler, DDIM and DPM++ 2M ignore them.  The
+initial latents are multiplied by sb(sigma_0) on the device, inside the captured pass and therefore after a variation's blend.
 """
 from __future__ import annotations
 
@@ -34,6 +38,7 @@ from .config import TEXT_SEQ_LEN, VAE_SCALE_FACTOR
 from .lib import LcmHipError
 from .model import ControlNetHip, UNetHip, VAEDecoderHip, VAEEncoderHip
 from .scheduler import LCMSchedule
+from . import samplers as _samplers
 
 
 def guidance_scale_embedding(w: np.ndarray, dim: int) -> np.ndarray:
@@ -188,7 +193,7 @@ class _Plan:
 
     FROM_STATE = ("from-state", "inpaint")
 
-    def __init__(self, pipe, B, h, w, steps, do_cfg, lane=None, refine=None, control=None, kind=None, n_ctx=1):
+    def __init__(self, pipe, B, h, w, steps, do_cfg, lane=None, refine=None, control=None, kind=None, n_ctx=1, sampler=None):
         # Every zero-fill below must be ordered before the first use on the lane's (non-blocking) stream: allocate
         # under that stream, or a fill still queued on the null stream can land AFTER the request's uploads.
         self.lane = lane if lane is not None else pipe.lanes[0]
@@ -197,8 +202,19 @@ class _Plan:
         self.kind = kind              # None | "latents" | "from-state" (the stages of a hires request) | "inpaint"
         self.init_img = None          # inpaint: the encoder stage's picture buffer (uint8 [B,H,W,3]), set by generate_inpaint
         self.n_ctx = int(n_ctx)       # 77-token chunks of the prompt: the cross-attention context is 77 n_ctx rows per image
+        # samplers.Tables of an Euler / Euler a / DDIM / DPM++ 2M plan (the pass is LcmHipPipeline._sampler_pass); None: LCM
+        self.sampler = None
+        if sampler is not None:
+            name, schedule = sampler
+            try:
+                self.sampler = (_samplers.img2img_tables(pipe.sched, name, schedule, steps, refine[0]) if kind in self.FROM_STATE
+                                else _samplers.tables(pipe.sched, name, schedule, steps))
+            except ValueError as e:
+                raise LcmHipError(str(e))
         with torch.cuda.stream(self.lane.stream):
             self._init(pipe, B, h, w, steps, do_cfg)
+            if self.sampler is not None:          # the previous step's x0 (DPM++ 2M reads it; every step writes it)
+                self.x0_prev = torch.zeros(B, 4, h, w, dtype=torch.float32, device=pipe.device)
 
     def _init(self, pipe, B, h, w, steps, do_cfg):
         dev = pipe.device
@@ -382,7 +398,7 @@ class LcmHipPipeline:
 
     @torch.inference_mode()
     def generate_img2img(self, prompt_embeds, seeds, images_u8, width, height, steps, strength, guidance_scale=1.0,
-                         negative_embeds=None, want_float=False, noises=None, lane=0):
+                         negative_embeds=None, want_float=False, noises=None, lane=0, sampler=None):
         """Image-to-image with the semantics of diffusers' LatentConsistencyModelImg2ImgPipeline: images_u8 uint8 [B,H,W,3] at the
         request's size -> AutoencoderKL encoder -> z = (mean + exp(0.5 clamp(logvar, -30, 20)) e0) scaling_factor -> re-noised to
         the first timestep of ``timesteps(steps, strength)`` with e1 -> ``steps`` LCM steps over that schedule -> decode.  The
@@ -390,7 +406,11 @@ class LcmHipPipeline:
         use_graph=False) and lcm_vae_posterior_renoise into the state of the "from-state" plan.  noises: optional
         per-request ``draw_noise_img2img`` results.  Returns the usual dict plus ``init_latents`` (host fp32 [B,4,h,w]: z) and
         ``unet_evals`` = steps (doubled under classifier-free guidance); with want_float also ``image`` and ``moments`` (host fp32
-        [B,8,h,w]: the posterior's mean | logvar)."""
+        [B,8,h,w]: the posterior's mean | logvar).
+        sampler = (name, "normal" | "karras") (samplers.py): the tail of that sampler's ``steps``-step schedule the strength leaves
+        (``samplers.img2img_tables``) in place of the LCM pass, from z re-noised to the tail's first noise level with e1 by the same
+        hand-over launch; the LCM bound on steps x strength does not apply.  The draws are the same; ``unet_evals`` counts the
+        tail's evaluations."""
         torch.cuda.set_device(self.device)
         pe = torch.as_tensor(prompt_embeds)
         B = pe.shape[0]
@@ -402,10 +422,13 @@ class LcmHipPipeline:
             raise LcmHipError(f"image-to-image strength {strength} outside (0, 1]")
         img, img_fit = self._sources(images_u8, B, (height, width, 3), "init images")
         do_cfg = self._do_cfg(guidance_scale, negative_embeds)
-        ts = self.sched.timesteps(steps, strength)       # diffusers' error for steps > original_steps x strength, before any plan
-        nsa, nsb = self.sched.renoise_coefficients(ts[0])
         h, w = height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR
-        P = self._from_state_plan(B, width, height, steps, strength, guidance_scale, lane, n_ctx=self._n_ctx(pe))
+        if sampler is None:
+            ts = self.sched.timesteps(steps, strength)   # diffusers' error for steps > original_steps x strength, before any plan
+            nsa, nsb = self.sched.renoise_coefficients(ts[0])
+        P = self._from_state_plan(B, width, height, steps, strength, guidance_scale, lane, n_ctx=self._n_ctx(pe), sampler=sampler)
+        if sampler is not None:
+            nsa, nsb = P.sampler.start
         L = P.lane
         self.lane_vae_encoder(L)                         # raises for a checkpoint without an encoder, before anything is queued
         E = self._enc_plan(L, B, height, width)
@@ -432,7 +455,8 @@ class LcmHipPipeline:
 
         out, _ = self._request([P], pe, negative_embeds, guidance_scale, upload, front, want_float=want_float,
                                more=lambda: E.h_z.copy_(P.xk[0], non_blocking=True))
-        out.update(init_latents=E.h_z.numpy().copy(), unet_evals=steps * (2 if do_cfg else 1))
+        out.update(init_latents=E.h_z.numpy().copy(),
+                   unet_evals=(steps if sampler is None else len(P.sampler.ts)) * (2 if do_cfg else 1))
         if want_float:
             out["moments"] = E.moments.cpu().numpy()
         return out
@@ -529,7 +553,9 @@ class LcmHipPipeline:
         that pass (unless the chain starts from cached latents in P.xk[0], re-noised by lcm_latents_renoise) followed by `run`
         passes over the strength-cut schedule.  A pass that another one follows ends in the hand-over step (x^k to P.xk, the
         re-noised state of the next pass to P.lat, one launch); the last pass ends in the plain `last` step and only its x goes
-        through the VAE."""
+        through the VAE.  A plan with a sampler (P.sampler) is one pass of ``_sampler_pass`` instead, decoded the same way."""
+        if P.sampler is not None:
+            return self._decode(P, self._sampler_pass(P, guidance, taps), want_float, taps)
         B, UB, h, w = P.B, P.UB, P.h, P.w
         unet, vae = P.lane.unet, P.lane.vae
         pred = self.sched.prediction_type
@@ -568,16 +594,7 @@ class LcmHipPipeline:
         ta_all, ta_c, ta_ts = hoist(unet, passes[0], wemb, aug), None, passes[0]
         cn = None
         if P.control is not None:
-            # ControlNet: the hint embedding ONCE per request (it depends on the hint alone), repeated for the unconditional
-            # half under classifier-free guidance (diffusers' guess_mode=False); its own cross-attention K/V and time embeddings
-            cn = self.lane_controlnet(P.lane)
-            n1 = B * h * w
-            cn.embed_hint(P.hint, B, h * VAE_SCALE_FACTOR, w * VAE_SCALE_FACTOR, P.hint_emb[:n1])
-            if P.do_cfg:
-                P.hint_emb[n1:].copy_(P.hint_emb[:n1])
-            if taps is not None:
-                taps["cn.hint_emb"] = P.hint_emb[:n1].reshape(B, h, w, -1).permute(0, 3, 1, 2).float().cpu()
-            kv_c = cn.encode_context(P.ehs, UB)
+            cn, kv_c = self._control_setup(P, taps)
             ta_c = hoist(cn, passes[0], None, None)
         for j, ts in enumerate(passes):
             if list(ts) != list(ta_ts):               # once per distinct schedule, reused across consecutive equal passes
@@ -615,6 +632,25 @@ class LcmHipPipeline:
             P.xk[run].copy_(state)
         if P.kind == "latents":                       # hires stage 1: nobody sees this picture, so nothing decodes it
             return state
+        return self._decode(P, state, want_float, taps)
+
+    def _control_setup(self, P: _Plan, taps=None):
+        """The part of a ControlNet plan's pass that is done once per request -> (the lane's ControlNet executor, its
+        cross-attention K/V): the hint embedding (it depends on the hint alone), repeated for the unconditional half under
+        classifier-free guidance (diffusers' guess_mode=False), and the ControlNet's own K/V of the prompt."""
+        B, h, w = P.B, P.h, P.w
+        cn = self.lane_controlnet(P.lane)
+        n1 = B * h * w
+        cn.embed_hint(P.hint, B, h * VAE_SCALE_FACTOR, w * VAE_SCALE_FACTOR, P.hint_emb[:n1])
+        if P.do_cfg:
+            P.hint_emb[n1:].copy_(P.hint_emb[:n1])
+        if taps is not None:
+            taps["cn.hint_emb"] = P.hint_emb[:n1].reshape(B, h, w, -1).permute(0, 3, 1, 2).float().cpu()
+        return cn, cn.encode_context(P.ehs, P.UB)
+
+    def _decode(self, P: _Plan, state, want_float=False, taps=None):
+        """The end of every pass that shows a picture: the pooled latents, the VAE decode and the RGB epilogue."""
+        B, h, w, vae = P.B, P.h, P.w, P.lane.vae
         ops.latents_pool8(state, P.pool8, B, h, w)
         if want_float and P.img_f32 is None:
             P.img_f32 = torch.zeros(B, h * 8, w * 8, 3, dtype=torch.float32, device=self.device)
@@ -623,7 +659,58 @@ class LcmHipPipeline:
             ops.inpaint_composite_rgb8(P.rgb, P.init_img, P.alpha, B, h * VAE_SCALE_FACTOR, w * VAE_SCALE_FACTOR)
         return state
 
-    def plan(self, B, h, w, steps, do_cfg=False, guidance=None, lane=0, refine=None, control=None, kind=None, n_ctx=1) -> _Plan:
+    def _sampler_pass(self, P: _Plan, guidance: float, taps=None):
+        """The pass of a plan with a sampler (P.sampler: samplers.Tables; include/lcm_hip.h, samplers): Euler, Euler a, DDIM or
+        DPM++ 2M over the plan's own noise levels -- a plain or ControlNet plan from the initial latents, a from-state plan
+        (image-to-image) from the state the posterior hand-over wrote.  The initial noise is scaled by sb(sigma_0) HERE, on the
+        device and inside the captured graph, i.e. after a variation's blend into P.lat0 (lcm_latents_renoise with weight 0 on
+        its second operand: one launch that also fills both classifier-free halves); DDIM starts from the noise itself.  The
+        UNet -- and the ControlNet -- are evaluated at the step's fractional timestep: nothing truncates it.  Every step is one
+        lcm_sampler_step launch; under classifier-free guidance it writes both halves of the state.  Euler a reads the
+        request's step noises in draw order; the deterministic samplers read none.  -> the state (the prompt half)."""
+        T = P.sampler
+        B, UB, h, w = P.B, P.UB, P.h, P.w
+        unet = P.lane.unet
+        pred = self.sched.prediction_type
+        from_state = P.kind in P.FROM_STATE
+        ni = 1 if from_state else 0                   # P.noise[0] of a from-state plan is e1, the hand-over's draw
+        if not from_state:                            # (a from-state plan: lcm_vae_posterior_renoise wrote P.lat and P.xk[0])
+            if taps is not None:
+                taps["latents0"] = P.lat0.cpu()       # the initial latents as the pass reads them (after a variation's blend)
+            if T.init_scale is not None:
+                ops.latents_renoise(P.lat0, P.lat0, T.init_scale, 0.0, P.lat, B, h, w, dup=P.do_cfg)
+            elif P.do_cfg:
+                P.lat[:B].copy_(P.lat0)
+                P.lat[B:].copy_(P.lat0)
+            else:
+                P.lat.copy_(P.lat0)
+        kv = unet.encode_context(P.ehs, UB)
+        wemb = P.wemb if unet.has_cond else None
+        state = P.lat[B:] if P.do_cfg else P.lat
+        eps = P.eps[B:] if P.do_cfg else P.eps
+        kw = dict(eps_uncond=P.eps[:B], guidance=guidance) if P.do_cfg else {}
+        ts = [float(t) for t in T.ts]
+        ta_all = unet.time_embed_all(ts, wemb, UB, None)          # len(ts) <= samplers.MAX_STEPS <= MAX_HOISTED_STEPS
+        cn = ta_c = None
+        if P.control is not None:
+            cn, kv_c = self._control_setup(P, taps)
+            ta_c = cn.time_embed_all(ts, None, UB, None)
+        for i, t in enumerate(ts):
+            rows, tap1 = slice(i * UB, (i + 1) * UB), taps if i == 0 else None
+            control = None
+            if cn is not None:
+                feats, mid_f = cn.forward(P.lat, t, kv_c, UB, h, w, P.hint_emb, taps=tap1, ta=ta_c[rows])
+                control = (cn, feats, mid_f, P.control)
+            unet.forward(P.lat, t, kv, wemb, UB, h, w, P.eps, taps=tap1, ta=ta_all[rows], control=control)
+            c_sa, c_sb, cx, c0, c1, c_n = T.coefs[i]
+            ops.sampler_step(eps, state, P.x0_prev, P.noise[ni + i] if c_n != 0.0 else None, c_sa, c_sb, cx, c0, c1, c_n, B, h, w,
+                             pred=pred, dup=P.do_cfg, **kw)
+        if P.xk is not None:
+            P.xk[1].copy_(state)
+        return state
+
+    def plan(self, B, h, w, steps, do_cfg=False, guidance=None, lane=0, refine=None, control=None, kind=None, n_ctx=1,
+             sampler=None) -> _Plan:
         # classifier-free guidance bakes the guidance value into the captured step kernels: one plan per value
         key = (B, h, w, steps, do_cfg, round(float(guidance), 4) if do_cfg and guidance is not None else None)
         if refine is not None:                       # (d, passes to run, starts from cached latents): a chain of its own
@@ -634,6 +721,8 @@ class LcmHipPipeline:
             key = key + (kind,)
         if int(n_ctx) != 1:                          # a long prompt: 77 n_ctx context rows (other buffers, other launches)
             key = key + ("ctx", int(n_ctx))
+        if sampler is not None:                      # Euler / Euler a / DDIM / DPM++ 2M: (canonical name, "normal" | "karras")
+            key = key + ("sampler", str(sampler[0]), str(sampler[1]))
         L = self.lane(lane)
         P = L.plans.get(key)
         if P is None:
@@ -641,7 +730,8 @@ class LcmHipPipeline:
                 P = L.plans.get(key)
                 if P is None:
                     P = _Plan(self, B, h, w, steps, do_cfg, L, refine=refine,
-                              control=None if control is None else round(float(control), 6), kind=kind, n_ctx=n_ctx)
+                              control=None if control is None else round(float(control), 6), kind=kind, n_ctx=n_ctx,
+                              sampler=None if sampler is None else (str(sampler[0]), str(sampler[1])))
                     L.plans[key] = P
         return P
 
@@ -767,11 +857,12 @@ class LcmHipPipeline:
             raise LcmHipError(f"prompt embeddings of shape {tuple(pe.shape)}: expected [B, {TEXT_SEQ_LEN} n, ctx]")
         return rows // TEXT_SEQ_LEN
 
-    def _from_state_plan(self, B, width, height, steps, strength, guidance_scale, lane, kind="from-state", n_ctx=1) -> _Plan:
+    def _from_state_plan(self, B, width, height, steps, strength, guidance_scale, lane, kind="from-state", n_ctx=1,
+                         sampler=None) -> _Plan:
         """The plan of one strength-cut pass that starts from a state the hand-over launch of a front stage wrote (hires
         stage 2, image-to-image; kind "inpaint": the masked pass of an inpaint request)."""
         return self.plan(B, height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR, int(steps), self._do_cfg(guidance_scale),
-                         guidance_scale, lane=lane, refine=(float(strength), 1, True), kind=kind, n_ctx=n_ctx)
+                         guidance_scale, lane=lane, refine=(float(strength), 1, True), kind=kind, n_ctx=n_ctx, sampler=sampler)
 
     def _recorded_need(self, holder, L: _Lane, run) -> int:
         """_need_of one eager run() recorded on the lane's stream; remembered on ``holder`` (a plan)."""
@@ -818,21 +909,22 @@ class LcmHipPipeline:
         enc = self.lane_vae_encoder(L)
         return self._recorded_need(E, L, lambda: enc.encode(E.img, 1, height, width))
 
-    def _batch_cap(self, width, height, steps, strength, guidance_scale, lane, sizes, other_need=0, n_ctx=1) -> int:
+    def _batch_cap(self, width, height, steps, strength, guidance_scale, lane, sizes, other_need=0, n_ctx=1, sampler=None) -> int:
         """The largest pass size of ``sizes`` at which the from-state pass at width x height -- and a stage of ``other_need``
         bytes per request before it on the same stream -- fits the lane's split-K workspace (at least the smallest: a batch-1
         pass that does not fit raises the library's loud error when it runs)."""
-        P = self._from_state_plan(1, width, height, steps, strength, guidance_scale, lane, n_ctx=n_ctx)
+        P = self._from_state_plan(1, width, height, steps, strength, guidance_scale, lane, n_ctx=n_ctx, sampler=sampler)
         per_request = max(self.splitk_need(P) * (2 if P.do_cfg else 1), other_need)   # classifier-free guidance: two UNet rows
         fit = [n for n in sorted(sizes) if n * per_request <= P.lane.splitk_ws.numel() * 4]
         return fit[-1] if fit else min(sizes)
 
-    def img2img_batch_cap(self, width, height, steps, strength, guidance_scale=1.0, lane=0, sizes=(1, 2, 4, 8), n_ctx=1) -> int:
+    def img2img_batch_cap(self, width, height, steps, strength, guidance_scale=1.0, lane=0, sizes=(1, 2, 4, 8), n_ctx=1,
+                          sampler=None) -> int:
         """The largest pass size of ``sizes`` at which BOTH stages of an image-to-image request at width x height fit the lane's
         split-K workspace: the strength-cut pass (hires_batch_cap's count, doubled rows under classifier-free guidance) and the
         encoder stage.  The stages run one after the other on one stream, so the need is the larger of the two."""
         return self._batch_cap(width, height, steps, strength, guidance_scale, lane, sizes,
-                               self.encoder_splitk_need(width, height, lane), n_ctx=n_ctx)
+                               self.encoder_splitk_need(width, height, lane), n_ctx=n_ctx, sampler=sampler)
 
     def inpaint_batch_cap(self, width, height, steps, strength, guidance_scale=1.0, lane=0, sizes=(1, 2, 4, 8), n_ctx=1) -> int:
         """img2img_batch_cap for an inpaint request: its masked pass runs the same contractions as the image-to-image pass (the
@@ -953,7 +1045,7 @@ class LcmHipPipeline:
     @torch.inference_mode()
     def generate(self, prompt_embeds, seeds, width, height, steps, guidance_scale=1.0, negative_embeds=None,
                  want_float=False, taps=None, latents=None, added=None, negative_added=None, noises=None, lane=0,
-                 strength=None, passes=0, start=None, control=None, hires=None, preprocess=None, variation=None):
+                 strength=None, passes=0, start=None, control=None, hires=None, preprocess=None, variation=None, sampler=None):
         """prompt_embeds: [B,77 n,ctx] (any float dtype, host or device; n chunks of a long prompt, concatenated: the
         plan, its graph and its cross-attention launches are those of n -- n = 1 is the plan of always); seeds: B ints.  noises: optional per-request
         ``draw_noise(seed, h, w, steps - 1, init_noise_sigma)`` results drawn ahead by the callers (the worker's pool
@@ -984,8 +1076,19 @@ class LcmHipPipeline:
         lcm_noise_variation_f32 for the whole batch, on the lane's stream between the uploads and the captured pass; slots with
         None are not touched, and a call without any variation queues nothing.  It is no part of the plan key.  A chain that
         starts from cached latents (start=) never reads the initial latents, so nothing is launched there.
+        sampler = (name, "normal" | "karras") with name one of samplers.py's Euler, Euler a, DDIM, DPM++ 2M: the pass steps with that
+        sampler (``_sampler_pass``; include/lcm_hip.h, samplers) instead of the LCM sampler.  It is part of the plan key.  The
+        request draws exactly what it draws without one; Euler a reads the step noises, the others ignore them.  Combined with
+        control, variation and long prompts; not with passes, hires or SDXL conditioning.
         Returns dict(rgb uint8 [B,H,W,3] (host), latents fp32 [B,4,h,w] (host), pool8 fp16 [B,4,8,8] (host))."""
         torch.cuda.set_device(self.device)        # the pool may call from a thread other than the constructing one
+        if sampler is not None:
+            if hires is not None or passes or start is not None or (strength is not None and float(strength) != 1.0):
+                raise LcmHipError("a sampler is not combined with hires fix or refinement passes")
+            if self.unet.has_added:
+                raise LcmHipError("samplers are not served for SDXL-family UNets")
+            if not 1 <= int(steps) <= _samplers.MAX_STEPS:
+                raise LcmHipError(f"num_inference_steps={int(steps)} outside 1..{_samplers.MAX_STEPS} with a sampler")
         if hires is not None:
             if passes or start is not None or (strength is not None and float(strength) != 1.0):
                 raise LcmHipError("hires fix is not combined with refinement passes")
@@ -1036,7 +1139,8 @@ class LcmHipPipeline:
                 raise LcmHipError("a ControlNet preprocessor needs a hint to work on (control=)")
             if not ((pre[0] == "canny" and len(pre) == 3) or pre == ("invert",)):
                 raise LcmHipError(f"unknown ControlNet preprocessor {pre!r}: expected ('canny', low, high) or ('invert',)")
-        P = self.plan(B, h, w, steps, do_cfg, guidance_scale, lane=lane, refine=refine, control=cscale, n_ctx=self._n_ctx(pe))
+        P = self.plan(B, h, w, steps, do_cfg, guidance_scale, lane=lane, refine=refine, control=cscale, n_ctx=self._n_ctx(pe),
+                      sampler=sampler)
         with torch.cuda.stream(P.lane.stream):       # latents= and the hint may be device tensors
             for b, s in enumerate(seeds):
                 if latents is not None:
