@@ -175,12 +175,25 @@ class LoraStyle:
         if weight == self.current:
             return
         for n, d in self.delta.items():
-            ops.axpy(self.base[n], d, weight, self.unet.w[n])
+            _merge(self.base[n], d, weight, self.unet.w[n])
             if n in self.cdelta:
                 stem = n[:-2]
-                ops.ln_fold_refresh(self.unet.w[n], self.unet.w[stem + ".g"], self.cbase[n], self.cdelta[n], weight,
-                                    self.unet.w[stem + ".c"])
+                if weight == 0.0:
+                    self.unet.w[stem + ".c"].copy_(self.cbase[n])
+                    ops.ln_fold_refresh(self.unet.w[n], self.unet.w[stem + ".g"])
+                else:
+                    ops.ln_fold_refresh(self.unet.w[n], self.unet.w[stem + ".g"], self.cbase[n], self.cdelta[n], weight,
+                                        self.unet.w[stem + ".c"])
         self.current = weight
+
+
+def _merge(base, delta, weight, out):
+    """out = base + weight * delta in place.  Weight 0 copies the base instead: fp16 checkpoints hold negative zeros, and
+    -0 + 0 * delta is +0 for delta >= 0, so the kernel's sum would not restore the base bit for bit."""
+    if weight == 0.0:
+        out.copy_(base)
+    else:
+        ops.axpy(base, delta, weight, out)
 
 
 # ---- text-encoder LoRA ---------------------------------------------------------------------------
@@ -245,7 +258,7 @@ class ClipLora:
         if weight == self.current:
             return
         for n, d in self.delta.items():
-            ops.axpy(self.base[n], d, weight, self.enc.w[n])
+            _merge(self.base[n], d, weight, self.enc.w[n])
         self.current = weight
 
 
