@@ -112,6 +112,20 @@ int lcm_plan_clear(void);
 /* the K partition a contraction of this per-image shape runs with (ph = 1: phase-decomposed upsample conv) */
 int lcm_canonical_splits(int kind, int m_img, int N, int K, int aux, int ph);
 
+/* Narrow tiles: a second, exact-shape table for batch-1 launches whose only real work is streaming weights (the 16^2 and
+ * 8^2 UNet levels: 64 / 256 rows x 1280 channels put 80-200 workgroups on 256 CUs).  A 64 x 32 tile halves the weight
+ * bytes each workgroup streams and doubles the workgroups.  Keys are those of the plan table, on the TOTAL shape of the
+ * launch: kind 0 = (0, M, N, K, batch), kind 2 = (2, M, N, K, (W_out << 1) | has_gn).  Only bn = 32 with N % 32 == 0 is
+ * accepted (LCM_EINVAL otherwise).  A hit replaces the tile width of the launch and nothing else -- the K partition, the
+ * ring depth / taps per step and the statistics slabs are those of the wide launch, so results are bit-identical
+ * (Determinism, above) -- and only where the launch is unbatched in z, has no GEGLU / activation epilogue, is not segmented
+ * and not GroupNorm-fused; every other launch ignores the table.  The package installs narrow_plans_gfx950.json (shapes
+ * measured faster cold on an MI355X, tools/make_narrow_plans.py) when the library is loaded; LCM_TUNED_PLANS=0 skips it. */
+int lcm_narrow_set(int kind, int M, int N, int K, int aux, int bn);
+int lcm_narrow_clear(void);
+/* process-wide switch over the whole narrow table (A/B runs); default on */
+int lcm_set_narrow_tiles(int on);
+
 /* ---- LayerNorm -> Linear as one contraction (BasicTransformerBlock: norm1 -> attn1.to_q|k|v, norm2 -> attn2.to_q,
  * norm3 -> ff.net.0.proj) ----
  *   LN(x) W^T + b  =  rstd[m] * (sum_k x[m][k] W'[n][k] - mean[m] * ln_g[n]) + ln_c[n]

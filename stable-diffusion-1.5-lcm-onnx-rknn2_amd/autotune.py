@@ -72,6 +72,33 @@ def _candidates(key, meta, ws_bytes, cold=False, tune_splits=False):
     return out
 
 
+def _narrow_candidate(key, meta):
+    """Whether the 32-column tile (ops.narrow_set) is one more candidate for this launch shape: the launches the library
+    honours a narrow entry on (plain GEMM unbatched in z, plain stride-1 halo conv), and only where the 64-wide grid x parts
+    leaves CUs without a workgroup (<= 256)."""
+    kind, M, N, K, aux = key
+    if N % 32 or meta.get("geglu") or meta.get("phases", 1) == 4:
+        return False
+    if not ((kind == 0 and aux == 1 and not meta["halo"]) or (kind == 2 and meta["halo"] and not (aux & 1))):
+        return False
+    return -(-M // 64) * -(-N // 64) * _canonical_splits(key, meta, meta.get("m_img", M)) <= 256
+
+
+_NARROW_WINS = {}        # narrow entries this process knows of (installed at load or won here)
+
+
+def _save_narrow(key):
+    """A first-use win goes beside the plan cache (<LCM_TUNE_CACHE>.narrow), never into it: the plan table keeps its tiles."""
+    import json
+    from . import lib as _lib
+    p = _cache_path()
+    if p:
+        tab = _lib.read_narrow(p + ".narrow")
+        tab[key] = 32
+        with open(p + ".narrow", "w") as f:
+            json.dump({",".join(str(v) for v in k): bn for k, bn in tab.items()}, f)
+
+
 def _time(fn, reps):
     fn()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -137,6 +164,9 @@ def autotune(records, ws_bytes, reps=None, verbose=False, cold=False, tune_split
     reps = reps or int(os.environ.get("LCM_AUTOTUNE_REPS", "6"))
     seen, chosen = {}, {}
     cache = _load_cache()
+    from . import lib as _lib
+    narrow = _NARROW_WINS
+    narrow.update(_lib.narrow_plans())            # the narrow table as installed: shipped file + earlier first-use wins
     dirty = False
     for key, meta, fn in records:
         seen.setdefault(key, (meta, fn))
@@ -161,6 +191,15 @@ def autotune(records, ws_bytes, reps=None, verbose=False, cold=False, tune_split
             if best is None or ms < best[4]:
                 best = (bm, bn, s, v, ms)
         ops.plan_set(key[0], key[1], key[2], key[3], key[4], *best[:4])
+        if cold and key not in narrow and _narrow_candidate(key, meta):
+            ops.narrow_set(*key)                      # the winner's launch with a 32-column tile: one more candidate
+            if _time_cold(fn, reps) < best[4]:
+                narrow[key] = 32
+                _save_narrow(key)
+            else:                                     # (the table has no per-key erase)
+                ops.narrow_clear()
+                for k in narrow:
+                    ops.narrow_set(*k)
         chosen[key] = best
         cache[key] = best
         dirty = True

@@ -499,6 +499,7 @@ extern float* lcm_splitk_workspace(long long* bytes, hipStream_t s);
 extern void lcm_tuning(int* target_wgs, int* max_splits, int* min_wgs);
 extern int lcm_split_policy(int m_img, int sp);
 extern bool lcm_plan_get(int kind, int M, int N, int K, int aux, int* bm, int* bn, int* splits, int* variant);
+extern int lcm_narrow_get(int kind, int M, int N, int K, int aux);
 
 static int g_halo_pipe_below = 768;      // workgroup count under which the pipelined (WS=3) variant is used
 
@@ -592,6 +593,42 @@ static void launch_halo(HaloParams& hp, hipStream_t s, int force) {     // force
     lcm_prof_start(nm, s);
     if (staged) hipLaunchKernelGGL((conv_halo_kernel<TH, TW, BN, XFORM, PH, 0, 1>), grid, dim3(256), smem, s, hp);
     else hipLaunchKernelGGL((conv_halo_kernel<TH, TW, BN, XFORM, PH>), grid, dim3(256), smem, s, hp);
+    lcm_prof_stop(s);
+}
+
+// The 32-channel tile of the narrow table (igemm.hip): the pipelined kernel with the ring depth and taps per step of the
+// 64-channel tile -- a kernel row of taps per step where the wide launch takes that form (plan variant 3), else one tap.
+template <int TH, int TW>
+static void launch_halo_narrow(HaloParams& hp, hipStream_t s, int force) {
+    constexpr int HROWS_PAD = ((TH + 2) * (TW + 2) + 7) / 8 * 8;
+    constexpr int BN = 32, WS = 3;
+    hp.tiles_y = (hp.H + TH - 1) / TH;
+    hp.tiles_x = (hp.W + TW - 1) / TW;
+    hp.g.ntiles = hp.g.N / BN;
+    dim3 grid(hp.g.mtiles * hp.g.ntiles, hp.g.splits, 1);
+    char nm[64];
+    if (force == 3) {
+        constexpr int smem = 2 * HROWS_PAD * 128 + WS * 3 * BN * 128;
+        static LcmDevOnce attr_once;
+        if (auto once_guard = attr_once.first()) {
+            once_guard.check(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_pipe_kernel<TH, TW, BN, WS, 0, 3>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+        }
+        snprintf(nm, sizeof(nm), "conv_halo_pipe_kernel<%d, %d, %d, %d, 0, 3>%s", TH, TW, BN, WS, hp.g.splits > 1 ? " +splitk" : "");
+        lcm_prof_start(nm, s);
+        hipLaunchKernelGGL((conv_halo_pipe_kernel<TH, TW, BN, WS, 0, 3>), grid, dim3(256), smem, s, hp);
+        lcm_prof_stop(s);
+        return;
+    }
+    constexpr int smem = 2 * HROWS_PAD * 128 + WS * BN * 128;
+    static LcmDevOnce attr_once1;
+    if (auto once_guard = attr_once1.first()) {
+        once_guard.check(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_pipe_kernel<TH, TW, BN, WS, 0, 1>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+    }
+    snprintf(nm, sizeof(nm), "conv_halo_pipe_kernel<%d, %d, %d, %d, 0, 1>%s", TH, TW, BN, WS, hp.g.splits > 1 ? " +splitk" : "");
+    lcm_prof_start(nm, s);
+    hipLaunchKernelGGL((conv_halo_pipe_kernel<TH, TW, BN, WS, 0, 1>), grid, dim3(256), smem, s, hp);
     lcm_prof_stop(s);
 }
 
@@ -697,6 +734,15 @@ int lcm_conv_halo_launch(HaloParams& hp, int B, hipStream_t s, int* slabs_per_im
     }
     const bool xf = hp.gn_scale != nullptr;
     if (ph && xf) return 1;
+    // narrow table: plain stride-1 launches (no phases, no fused GroupNorm), not segmented, that would take the pipelined kernel
+    if (!ph && !xf && p.seg_parts == 1 && force != 1 && (force != 0 || (long long)p.mtiles * (p.N / bn) * p.splits < g_halo_pipe_below) &&
+        lcm_narrow_get(2, p.M, p.N, p.K, hp.W << 1) == 32) {
+        if (th == 8 && TW == 16) launch_halo_narrow<8, 16>(hp, s, force);
+        else if (th == 4 && TW == 16) launch_halo_narrow<4, 16>(hp, s, force);
+        else launch_halo_narrow<8, 8>(hp, s, force);
+        if (p.splits > 1) lcm_launch_splitk_reduce(p, s);
+        return 0;
+    }
 #define HALO_CASE(TH_, TW_, BN_)                                                           \
     if (th == TH_ && TW == TW_ && bn == BN_) {                                             \
         if (ph) launch_halo<TH_, TW_, BN_, 0, 1>(hp, s, force);                            \

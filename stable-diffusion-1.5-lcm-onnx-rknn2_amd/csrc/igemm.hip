@@ -640,6 +640,43 @@ bool lcm_plan_get(int kind, int M, int N, int K, int aux, int* bm, int* bn, int*
     return true;
 }
 
+// ---- narrow tiles: an exact-shape table beside the plan table ----
+// Batch-1 launches of the low-resolution levels (M = 64 / 256 rows, N = 1280) put 80-200 workgroups on 256 CUs, and each of
+// them streams a 64-row weight tile at the per-CU fill rate: their time is one workgroup's K walk.  A 32-column tile halves
+// the weight bytes per workgroup and doubles the workgroups.  The tile is a launch parameter (see "What decides the numbers"
+// below): the K partition, the k-tile order of every output element and the canonical statistics slabs are those of the wide
+// launch, so the table is bit-neutral.  It is keyed like the plan table on the TOTAL shape of the launch -- kind 0:
+// (0, M, N, K, batch); kind 2: (2, M, N, K, (W << 1) | xform) -- holds only shapes that were measured faster
+// (tools/make_narrow_plans.py), and is consulted after today's tile is chosen: a hit replaces bn by 32 and nothing else.
+static std::map<std::tuple<int, int, int, int, int>, int> g_narrow;
+static int g_narrow_on = 1;
+
+extern "C" int lcm_narrow_set(int kind, int M, int N, int K, int aux, int bn) {
+    if (bn != 32 || (kind != 0 && kind != 2) || M <= 0 || N <= 0 || N % 32 != 0) {
+        lcm_set_error("narrow_set: kind %d M %d N %d bn %d (only bn = 32 with N %% 32 == 0, kinds 0 and 2)", kind, M, N, bn);
+        return LCM_EINVAL;
+    }
+    std::lock_guard<std::mutex> lk(g_plans_mu);
+    g_narrow[std::make_tuple(kind, M, N, K, aux)] = bn;
+    return LCM_OK;
+}
+
+extern "C" int lcm_narrow_clear(void) {
+    std::lock_guard<std::mutex> lk(g_plans_mu);
+    g_narrow.clear();
+    return LCM_OK;
+}
+
+extern "C" int lcm_set_narrow_tiles(int on) { g_narrow_on = on ? 1 : 0; return LCM_OK; }
+
+// the narrow tile width of this exact launch shape, or 0
+int lcm_narrow_get(int kind, int M, int N, int K, int aux) {
+    if (!g_narrow_on) return 0;
+    std::lock_guard<std::mutex> lk(g_plans_mu);
+    auto it = g_narrow.find(std::make_tuple(kind, M, N, K, aux));
+    return it == g_narrow.end() ? 0 : it->second;
+}
+
 // Tile + split-K selection.
 //
 // What decides the numbers and what does not.  The fp32 summation order of an output element is fixed by the K
@@ -767,7 +804,7 @@ template <int BM, int BN, int MODE, int S, int LN = 0, int SEG = 0>
 static int launch_v2(IgemmParams& p, dim3 grid, hipStream_t s) {
     constexpr int smem = S * (BM + BN) * 128 + (LN ? 2 * BN * 4 : 0);       // LN: + this n-tile's ln_g | ln_c
     // the staged epilogue: a plain launch with a residual tile to fetch, the tile image fits the ring, strided z-batches excluded
-    constexpr bool can_stage = MODE == 0 && !LN && !SEG && S * (BM + BN) * 128 >= BM * BN * 2;
+    constexpr bool can_stage = MODE == 0 && !LN && !SEG && BN >= 64 && S * (BM + BN) * 128 >= BM * BN * 2;
     if constexpr (can_stage) if (g_staged_epi_gemm && p.res && p.splits == 1 && p.n_iters == 1 && p.epi == 0 && grid.z == 1) {
         static LcmDevOnce attr_once_e;
         if (auto once_guard = attr_once_e.first()) {
@@ -864,6 +901,25 @@ static int launch_cfg(IgemmParams& p, int batch, int splits, int plan_variant, h
     return LCM_OK;
 }
 
+// The 64 x 32 tile of the narrow table: a wave owns 32 rows x 16 columns (one n-fragment), so it still owns whole canonical
+// 32-row statistics slabs.  Ring depth 3 where the wide launch would run depth 3, else 4 -- the depths of the 64 x 64 tile.
+template <int LN>
+static int launch_narrow(IgemmParams& p, int splits, int depth, hipStream_t s) {
+    p.mtiles = (p.M + 63) / 64;
+    p.ntiles = p.N / 32;
+    p.splits = splits;
+    p.n_iters = 1;
+    dim3 grid(p.mtiles * p.ntiles, splits, 1);
+    if (depth == 3) launch_v2<64, 32, 0, 3, LN>(p, grid, s);
+    else launch_v2<64, 32, 0, 4, LN>(p, grid, s);
+    LCM_CHECK_LAUNCH("igemm");
+    if (splits > 1) {
+        lcm_launch_splitk_reduce(p, s);
+        LCM_CHECK_LAUNCH("splitk_reduce");
+    }
+    return LCM_OK;
+}
+
 // Fused-statistics bookkeeping: `img_rows` = output rows per image.  On return *slabs_per_image is the number of
 // [N][2] partial rows the launch wrote per image (0 = statistics not produced; the caller then runs the standalone
 // statistics kernel).
@@ -906,6 +962,12 @@ static int launch_igemm(IgemmParams& p, int batch, hipStream_t s, int img_rows, 
                       "(lcm_set_workspace / LCM_SPLITK_WS_MB)", splits, p.M, p.N,
                       ((long long)splits * p.M * p.N * 4 + (1 << 20) - 1) >> 20, wsb >> 20);
         return LCM_EINVAL;
+    }
+    if constexpr (MODE == 0) {       // narrow table: plain / LayerNorm-fold launches, unbatched in z, not segmented, ring depth 3 or 4
+        const int v = g_variant >= 0 ? g_variant : variant;
+        if (batch == 1 && p.epi == 0 && p.seg_parts == 1 && (v < 0 || (v >= 3 && v <= 5)) &&
+            lcm_narrow_get(0, p.M, p.N, p.K, batch) == 32)
+            return p.ln_g ? launch_narrow<1>(p, splits, v, s) : launch_narrow<0>(p, splits, v, s);
     }
     const int code = t.bm * 1000 + t.bn;
     if constexpr (MODE == 0) if (p.ln_g) {     // LayerNorm-folded GEMM: its own instantiations (compile-time switch in the K loop)

@@ -120,6 +120,9 @@ _SIGS = {
     "lcm_set_gn_fused_bytes": [_i64],
     "lcm_plan_set": [_i] * 9,
     "lcm_plan_clear": [],
+    "lcm_narrow_set": [_i] * 6,
+    "lcm_narrow_clear": [],
+    "lcm_set_narrow_tiles": [_i],
     "lcm_canonical_splits": [_i] * 6,
     "lcm_conv3x3_gn_f16": [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i64,
                            C.POINTER(_i), _vp],
@@ -224,6 +227,33 @@ def _install_plans(lib):
     for (kind, M, N, K, aux), val in known_plans().items():
         bm, bn, sp, v = (int(x) for x in val[:4])
         lib.lcm_plan_set(kind, M, N, K, aux, bm, bn, sp, v)
+    for (kind, M, N, K, aux), bn in narrow_plans().items():
+        lib.lcm_narrow_set(kind, M, N, K, aux, bn)
+
+
+PACKAGED_NARROW = os.path.join(_HERE, "narrow_plans_gfx950.json")
+
+
+def read_narrow(path) -> dict:
+    import json
+    try:
+        with open(path) as f:
+            return {tuple(int(v) for v in k.split(",")): int(bn) for k, bn in json.load(f).items()}
+    except Exception:
+        return {}
+
+
+def narrow_plans() -> dict:
+    """The narrow-tile table (include/lcm_hip.h, lcm_narrow_set): exact launch shapes that run a 32-column tile, measured
+    faster cold on an MI355X (tools/make_narrow_plans.py), overlaid by the first-use tuner's wins (<LCM_TUNE_CACHE>.narrow).
+    A table of its own: the plan table (``known_plans``) keeps its tiles.  LCM_TUNED_PLANS=0 ignores the shipped file."""
+    plans = {}
+    if os.environ.get("LCM_TUNED_PLANS", "1") != "0" and os.path.exists(PACKAGED_NARROW):
+        plans.update(read_narrow(PACKAGED_NARROW))
+    p = os.environ.get("LCM_TUNE_CACHE", "")
+    if p and os.path.exists(p + ".narrow"):
+        plans.update(read_narrow(p + ".narrow"))
+    return plans
 
 
 def check(rc: int, what: str = ""):

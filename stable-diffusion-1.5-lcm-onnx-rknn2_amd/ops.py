@@ -88,9 +88,24 @@ def plan_clear():
     _lib.check(_lib.load().lcm_plan_clear(), "lcm_plan_clear")
 
 
+def narrow_set(kind, M, N, K, aux, bn=32):
+    """This exact launch shape runs a 32-column tile (include/lcm_hip.h, lcm_narrow_set): bit-neutral."""
+    _lib.check(_lib.load().lcm_narrow_set(int(kind), int(M), int(N), int(K), int(aux), int(bn)), "lcm_narrow_set")
+
+
+def narrow_clear():
+    _lib.check(_lib.load().lcm_narrow_clear(), "lcm_narrow_clear")
+
+
+def set_narrow_tiles(on):
+    """Process-wide switch over the narrow table (A/B runs); default on."""
+    _lib.check(_lib.load().lcm_set_narrow_tiles(1 if on else 0), "lcm_set_narrow_tiles")
+
+
 def plan_reset():
-    """Back to the table the library is loaded with (shipped plans + LCM_TUNE_CACHE)."""
+    """Back to the tables the library is loaded with (shipped plans + LCM_TUNE_CACHE)."""
     plan_clear()
+    narrow_clear()
     _lib._install_plans(_lib.load())
 
 
