@@ -608,6 +608,41 @@ long long lcm_resize_ws_bytes(int C, int sw, int sh, int out_w, int out_h, int x
 int lcm_resize_lanczos_u8(const void* src, long long src_stride, int C, int sw, int sh, int out_w, int out_h, int x0, int y0, int w,
                           int h, void* dst, long long dst_stride, void* ws, long long ws_bytes, void* stream);
 
+/* ---- tile grid combine: the overlapping tiles of an SD-upscale request blended into one picture (csrc/grid.hip, DESIGN.md
+ * sections 3, 6; backends/sdupscale.py) ----
+ * The text below DEFINES the result bit for bit.  It is A1111's combine_grid, that is PIL's paste with an "L" mask, per channel
+ * byte (byte-equal to Pillow 12.2.0's paste in A1111's paste order at the geometries of tests/test_sdupscale_cpu.py; equality
+ * with A1111 itself is UNVERIFIED).
+ *   tiles_u8 uint8 [rows*cols][tile_h][tile_w][3], tile k = r * cols + c at offset (xs[c], ys[r]) of the picture;
+ *   out_u8 uint8 [H][W][3].  The descriptor is read during the call only and travels in the kernel's arguments.
+ *   m(i) = (255 * i) / overlap, integer division, for 0 <= i < overlap.
+ *   blend(p, t, m) = DIV255(p * (255 - m) + t * m),  DIV255(a) = ((a + 128) + ((a + 128) >> 8)) >> 8.
+ *   Row picture R_r(x, yy), 0 <= yy < tile_h: start at 0, then for c = 0 .. cols-1 in order, i = x - xs[c], t = tile (r, c) at (i, yy):
+ *     c == 0: if x < tile_w the value becomes t;
+ *     otherwise, if 0 <= i < overlap the value becomes blend(value, t, m(i));
+ *     otherwise, if overlap <= i < tile_w the value becomes t.
+ *   Output O(x, y): start at 0, then for r = 0 .. rows-1 in order, j = y - ys[r]:
+ *     r == 0: if y < tile_h the value becomes R_0(x, y);
+ *     otherwise, if 0 <= j < overlap the value becomes blend(value, R_r(x, j), m(j));
+ *     otherwise, if overlap <= j < tile_h the value becomes R_r(x, j).
+ *   overlap == 0: no blend region (A1111 divides by zero there: a stated deviation).
+ *   The offsets of an axis obey four facts (v = xs, n = cols, tile = tile_w, size = W; likewise ys): v[0] == 0; v strictly
+ *   increasing; v[k+1] - v[k] <= tile - overlap; v[n-1] + tile == size.  So every pixel lies under a tile's non-blend part and a
+ *   pixel may lie under three or more tiles of an axis.
+ * One launch, a pure gather: a thread owns four neighbouring pixels of one output row (dword stores where the row allows it), finds
+ * the covering rows and columns from the by-value offsets and folds forward from the last non-blend cover.  No LDS, no atomics, no
+ * workgroup waits for another; nothing allocates, synchronises or is read back; capturable.  tiles and out must not overlap.
+ * LCM_EINVAL before anything is enqueued: null pointers; cols or rows outside 1..32; tile_w or tile_h outside 1..4096; W or H
+ * outside tile..4096; overlap outside 0 .. min(tile_w, tile_h) - 1; xs / ys that break the four facts;
+ * rows * cols * tile_h * tile_w * 3 >= 2^31. */
+#define LCM_GRID_MAX_AXIS 32
+typedef struct lcm_grid_desc {
+    int W, H, tile_w, tile_h, overlap, cols, rows;
+    int xs[LCM_GRID_MAX_AXIS];
+    int ys[LCM_GRID_MAX_AXIS];
+} lcm_grid_desc;
+int lcm_grid_combine_rgb8(const void* tiles_u8, void* out_u8, const lcm_grid_desc* desc, void* stream);
+
 /* ---- adaptive_avg_pool2d(lat,(8,8)) -> fp16 [B,4,8,8] (run_job_with_latents, backends/cuda_worker.py:299-304) */
 int lcm_latents_pool8(const void* lat, void* out_f16, int B, int h, int w, void* stream);
 

@@ -18,6 +18,7 @@ Env (as the reference, backends/cuda_worker.py:43-61):
                              resampler on the lane's stream, or PIL on the caller's thread; the bytes are the same (backends/fit.py)
   LCM_SAMPLERS               request (default) | lcm: whether ``sampler_name`` / ``scheduler`` are read (backends/sampler.py); with lcm
                              every request is stepped by the LCM sampler, as before the fields were known
+  LCM_SDUPSCALE_MAX_TILES    the most tiles an SD-upscale request (``script_name``, backends/sdupscale.py) may have; default 64
   CUDA_DTYPE                 fp16 (default).  bf16 / fp32 -- which the reference honours -- are REFUSED unless LCM_HIP_DTYPE=fp16
                              says to run them in this backend's one arithmetic (fp16 operands, fp32 accumulation)
 """
@@ -47,6 +48,7 @@ from . import inpaint as _inpaint
 from . import prompt_syntax as _prompt
 from . import refine as _refine
 from . import sampler as _sampler
+from . import sdupscale as _sdupscale
 from . import variation as _variation
 
 
@@ -350,7 +352,8 @@ class _Engine:
         self._stats_lock = threading.Lock()
         self.stats = dict(unet_evals=0, refine_cache_hits=0, refine_cache_misses=0, refine_cache_puts=0, controlnet_evals=0,
                           hires_requests=0, img2img_requests=0, inpaint_requests=0, controlnet_preprocessed=0,
-                          resized_on_device=0, prompt_chunks=0, weighted_prompts=0, variation_requests=0, sampler_requests=0)
+                          resized_on_device=0, prompt_chunks=0, weighted_prompts=0, variation_requests=0, sampler_requests=0,
+                          sdupscale_requests=0, sdupscale_tiles=0)
         # ControlNet: where it comes from (CONTROLNET=<dir or file> | "synthetic" | None); loaded on the first request that
         # carries a hint, released with the pipeline
         self.controlnet_src = None
@@ -443,6 +446,7 @@ class _Engine:
         """One batched sampler pass for ``items`` = [(req, seed[, noise])], all of ``key``, on lane ``lane``;
         -> per-item (rgb, pool8 row)."""
         key, n_ctx = _prompt.split_ctx(key)          # a long-prompt pass: the kind's own key + ("ctx", n)
+        key, sdu = _sdupscale.split_key(key)         # SD-upscale jobs: the image-to-image key + ("sdupscale", overlap, upscaler, W, H)
         key, smp = _sampler.split_key(key)           # a sampler pass: the kind's own key + ("sampler", name, sigmas); None: LCM
         smp_kw = dict(sampler=smp) if smp is not None else {}
         width, height, steps, g, style_id, level = key[:6]
@@ -472,6 +476,14 @@ class _Engine:
                     res = self._run_capped(items, noises, pe, kw, cap, stream, "hires_requests", lambda idx, sub_pe, sub_noises, sub_kw:
                                            pipe.generate(sub_pe, [seeds[i] for i in idx], width, height, steps, g, noises=sub_noises,
                                                          lane=lane, hires=(tw, th, hr_steps, strength, mode), **var_kw(idx), **sub_kw))
+                elif sdu is not None:                # SD upscale: the jobs one after the other, each its tiles' passes + the combine
+                    cap = pipe.img2img_batch_cap(width, height, steps, key[7], g, lane=lane, sizes=self.batch_sizes, n_ctx=n_ctx, **smp_kw)
+                    res, done = [None] * len(items), {}
+                    for i, it in enumerate(items):
+                        if id(it) not in done:       # (a repeated item filled the plan size: served once)
+                            done[id(it)] = self._run_sdupscale(pipe, it, i, len(items), pe, kw, cap, lane, stream,
+                                                               (width, height, steps, key[7], g), smp_kw)
+                        res[i] = done[id(it)]
                 elif _img2img.is_img2img_key(key):   # key = plain key + (KEY_TAG, strength); items carry the fitted picture
                     cap = pipe.img2img_batch_cap(width, height, steps, key[7], g, lane=lane, sizes=self.batch_sizes, n_ctx=n_ctx, **smp_kw)
                     res = self._run_capped(items, noises, pe, kw, cap, stream, "img2img_requests", lambda idx, sub_pe, sub_noises, sub_kw:
@@ -556,6 +568,36 @@ class _Engine:
                 self.stats["refine_cache_puts"] += puts
             _take(res, out, idx)
         return res
+
+    def _run_sdupscale(self, pipe, item, i, n, pe, kw, cap, lane, stream, shape, smp_kw):
+        """One SD-upscale job (item ``i`` of the ``n`` the conditioning was encoded for): its T tiles in row-major order as
+        image-to-image passes of the largest plan size that fits both the tiles left and ``cap`` (tile k: seed + k, its own draws,
+        the request's conditioning row repeated), every pass's decoded pictures kept in the lane's tile store; then one combine
+        launch and one read-back of the W x H picture.  -> (rgb [H, W, 3], the pool8 row of tile 0).  ``unet_evals`` counts every
+        tile's evaluations."""
+        tile_w, tile_h, steps, strength, g = shape
+        req, seed, draws, pics, grid = item
+        T = len(pics)
+        seeds = _sdupscale.tile_seeds(seed, T)
+        store = pipe.grid_store(lane, T, tile_h, tile_w)
+        pool8, evals, k0 = None, 0, 0
+        for m in _sdupscale.pass_sizes(T, cap, self.batch_sizes):
+            with torch.cuda.stream(stream):          # the request's row, once per slot, behind the text encoder
+                sub_pe, sub_kw = _rows((pe, kw), [i] * m, n)
+            out = pipe.generate_img2img(sub_pe, seeds[k0:k0 + m], _fit.stack(pics[k0:k0 + m]), tile_w, tile_h, steps, strength, g,
+                                        noises=draws[k0:k0 + m] if draws is not None else None, lane=lane, tiles=(store, k0, m),
+                                        **smp_kw, **sub_kw)
+            if pool8 is None:
+                pool8 = out["pool8"][0:1]
+            evals += out["unet_evals"] * m
+            k0 += m
+        rgb = pipe.combine_grid(lane, store, grid.W, grid.H, grid.overlap, grid.xs, grid.ys)
+        with self._stats_lock:
+            self.stats["unet_evals"] += evals
+            self.stats["sdupscale_requests"] += 1
+            self.stats["sdupscale_tiles"] += T
+            self.stats["resized_on_device"] += int(any(_fit.is_pending(p) for p in pics))
+        return rgb, pool8
 
     def _run_capped(self, items, noises, pe, kw, cap, stream, stat, call):
         """A hires, image-to-image or inpaint batch as passes of at most ``cap`` items (the largest plan size whose split-K workspace
@@ -883,6 +925,8 @@ class HipLcmWorker:
         (backends/inpaint.py) they are inpaint requests with the plain key + ("inpaint", strength, mask_blur) instead.
         A request with a served ``sampler_name`` (backends/sampler.py; plain, ControlNet and image-to-image requests) appends
         ("sampler", canonical name, "karras" | "normal") to its kind's key: such jobs coalesce among themselves.
+        An SD-upscale request (``script_name``, backends/sdupscale.py) appends ("sdupscale", overlap, upscaler, W, H) to its
+        image-to-image key: such jobs may be drained together, then run one after the other -- tiles of two requests never share a pass.
         A prompt of n > 1 chunks (backends/prompt_syntax.py; under classifier-free guidance the longer of prompt and negative
         prompt counts) appends ("ctx", n) to whichever of these keys the request has: the pass has 77 n context rows.  With n == 1 --
         weighted or not, with or without a negative prompt -- the key is the one of always; the texts and ``clip_skip`` are per
@@ -908,6 +952,10 @@ class HipLcmWorker:
         inp = _inpaint.parse_inpaint(req)            # a mask without a picture raises here
         if i2i is not None:
             _fit.parse_resize_mode(req)              # its own error, for its own job; no part of the key (the picture is per image)
+        # SD upscale (``script_name``, backends/sdupscale.py): None for every request without the script -- today's key
+        sdu = _sdupscale.parse_sdupscale(req, i2i, width, height)
+        if sdu is not None and inp is not None:
+            raise RuntimeError(_sdupscale.NOT_COMBINED + "mask")
         # variation seeds / seed-resize (backends/variation.py): their own errors, for their own job; no part of the key -- the
         # variation is per image, plain and varied requests share passes
         if _variation.parse_variation(req, width, height) is not None and (i2i is not None or inp is not None):
@@ -938,7 +986,9 @@ class HipLcmWorker:
                 raise RuntimeError("init_image is not combined with refinement (denoise_strength < 1 or pass_number > 1)")
             if ctl is not None:
                 raise RuntimeError("init_image is not combined with controlnet_image")
-            return key + (_img2img.KEY_TAG, i2i[0]) + tail
+            # SD-upscale jobs: the image-to-image key + ("sdupscale", overlap, upscaler, W, H) -- never a pass with image-to-image
+            # jobs; W x H come from the parse (they depend on the picture)
+            return key + (_img2img.KEY_TAG, i2i[0]) + tail + _sdupscale.tail(sdu)
         if hr is not None:
             if rf is not None:
                 raise RuntimeError("enable_hr is not combined with refinement (denoise_strength < 1 or pass_number > 1)")
@@ -1007,6 +1057,7 @@ class HipLcmWorker:
         domain) or handed on at its own size as a ``fit.Pending`` for the lane's stream to fit (backends/fit.py)."""
         eng = self._engine
         key, _ = _prompt.split_ctx(key)              # the prompt's length changes nothing here
+        key, sdu = _sdupscale.split_key(key)
         key, smp = _sampler.split_key(key)           # a sampler draws exactly what the LCM sampler draws for the request
         seed = int(req.seed) if getattr(req, "seed", None) is not None else int(torch.randint(0, 100_000_000, (1,)).item())
         # the request's RNG stream (initial latents, then one draw per remaining step) is drawn HERE, on the caller's
@@ -1027,6 +1078,14 @@ class HipLcmWorker:
                 _refine.check_schedule(sched, steps, key[7])
             else:                                    # the LCM-only step bound does not apply; DDIM with no timestep left raises here
                 _sampler.check_img2img(sched, smp, steps, key[7])
+            if sdu is not None:
+                # SD upscale: tile k is the image-to-image request of its own pixels with seed + k -- its draws are that
+                # request's, its picture a window of the one resample grid (resize_mode is not applied: nothing is fitted to size)
+                _, _, _, _, g = _sdupscale.parse_sdupscale(req, _img2img.parse_img2img(req), key[0], key[1])
+                pics, _ = _sdupscale.tile_pictures(_img2img.parse_img2img(req)[1], g)
+                draws = ([draw_noise_img2img(s, h8, w8, steps) for s in _sdupscale.tile_seeds(seed, len(pics))]
+                         if self._drawable(key) else None)
+                return (req, seed, draws, pics, g)
             pic = _fit.prepare(_img2img.parse_img2img(req)[1], key[0], key[1], _fit.parse_resize_mode(req), _img2img.fit_init)
             return (req, seed, draw_noise_img2img(seed, h8, w8, steps) if self._drawable(key) else None, pic)
         if _hires.is_hires_key(key):                 # the schedule's own error first, then the draws at both shapes
@@ -1237,7 +1296,12 @@ class HipLcmWorker:
         for i, job in enumerate(jobs):
             req = job.req
             seeds.append(int(req.seed) if getattr(req, "seed", None) is not None else int(torch.randint(0, 100_000_000, (1,)).item()))
-            groups.setdefault(self._job_key(req), []).append(i)
+            key = self._job_key(req)
+            if _img2img.is_img2img_key(key) or _inpaint.is_inpaint_key(key) or _controlnet.is_control_key(key):
+                # these kinds (SD-upscale keys are image-to-image keys) carry an upload per item, which only ``_prepare`` builds
+                raise RuntimeError("run_jobs does not serve requests with an upload (init_image, mask, controlnet_image, SD upscale): "
+                                   "use run_job")
+            groups.setdefault(key, []).append(i)
         rgbs = [None] * len(jobs)
         sizes = self._engine.batch_sizes
         for key, idx in groups.items():
@@ -1275,6 +1339,8 @@ class HipLcmSDXLWorker(HipLcmWorker):
 
     @staticmethod
     def _job_key(req):
+        if _sdupscale.active(req):
+            raise RuntimeError(_sdupscale.SDXL_ERROR)
         if getattr(req, "enable_hr", None):
             raise RuntimeError("enable_hr: hires fix is not served by the SDXL worker (SD1.5 and SD 2.x only)")
         if getattr(req, "init_image", None) is not None or getattr(req, "init_images", None) is not None:

@@ -37,6 +37,14 @@ class VariationDesc(C.Structure):
 
 
 VARIATION_MAX_BATCH = 8    # LCM_VARIATION_MAX_BATCH
+GRID_MAX_AXIS = 32         # LCM_GRID_MAX_AXIS
+
+
+class GridDesc(C.Structure):
+    """lcm_grid_desc (include/lcm_hip.h): the tile grid of one lcm_grid_combine_rgb8 launch."""
+    _fields_ = [("W", _i), ("H", _i), ("tile_w", _i), ("tile_h", _i), ("overlap", _i), ("cols", _i), ("rows", _i),
+                ("xs", _i * GRID_MAX_AXIS), ("ys", _i * GRID_MAX_AXIS)]
+
 
 _SIGS = {
     "lcm_gemm_f16": [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _i,
@@ -81,6 +89,7 @@ _SIGS = {
     "lcm_canny_rgb8": [_vp, _vp, _vp, C.c_longlong, _i, _i, _i, _f, _f, _vp],
     "lcm_invert_u8": [_vp, _vp, C.c_longlong, _vp],
     "lcm_noise_variation_f32": [_vp, _i, _i, _i, C.POINTER(VariationDesc), _vp],
+    "lcm_grid_combine_rgb8": [_vp, _vp, C.POINTER(GridDesc), _vp],
     "lcm_resize_lanczos_u8": [_vp, C.c_longlong, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_longlong, _vp, C.c_longlong, _vp],
     "lcm_resize_tables": [_i, _i, _i, _i, _vp, C.c_longlong],
     "lcm_resize_plan_tables": [_i] * 8 + [_vp, C.c_longlong],

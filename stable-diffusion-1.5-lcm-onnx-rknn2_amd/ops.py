@@ -736,6 +736,30 @@ def resize_lanczos_u8(src, dst, ws, out_w, out_h, window=None):
     return dst
 
 
+def grid_desc(W, H, tile_w, tile_h, overlap, xs, ys):
+    """The lcm_grid_desc of a tile grid (include/lcm_hip.h): xs / ys are the tile offsets of the axes, at most 32 each."""
+    xs, ys = [int(v) for v in xs], [int(v) for v in ys]
+    if not (1 <= len(xs) <= _lib.GRID_MAX_AXIS and 1 <= len(ys) <= _lib.GRID_MAX_AXIS):
+        raise _lib.LcmHipError(f"grid_combine: {len(xs)} x {len(ys)} tiles, an axis holds 1..{_lib.GRID_MAX_AXIS}")
+    d = _lib.GridDesc(int(W), int(H), int(tile_w), int(tile_h), int(overlap), len(xs), len(ys))
+    d.xs[:len(xs)] = xs
+    d.ys[:len(ys)] = ys
+    return d
+
+
+def grid_combine_rgb8(tiles, out, desc):
+    """A1111's combine_grid of the tiles of one picture, one launch (lcm_grid_combine_rgb8, include/lcm_hip.h defines the bytes):
+    tiles uint8 [rows*cols, tile_h, tile_w, 3] (at least: a larger store's head is read), out uint8 [H, W, 3] (at least), both
+    contiguous device tensors; desc: ``grid_desc(...)`` or its argument tuple.  Nothing is read back."""
+    L = _lib.load()
+    d = desc if isinstance(desc, _lib.GridDesc) else grid_desc(*desc)
+    for t, name, n in ((tiles, "tiles", d.rows * d.cols * d.tile_h * d.tile_w * 3), (out, "output", d.H * d.W * 3)):
+        if t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() < max(n, 0):
+            raise _lib.LcmHipError(f"grid_combine: the {name} must be contiguous uint8 of at least {n} bytes, got {t.dtype} {tuple(t.shape)}")
+    _lib.check(L.lcm_grid_combine_rgb8(_p(tiles), _p(out), C.byref(d), _stream()), "lcm_grid_combine_rgb8")
+    return out
+
+
 def latents_pool8(lat, out, B, h, w):
     L = _lib.load()
     _lib.check(L.lcm_latents_pool8(_p(lat), _p(out), B, h, w, _stream()), "lcm_latents_pool8")

@@ -181,6 +181,9 @@ class _Lane:
         self.pre_ws = None            # ControlNet preprocessor (generate(preprocess=)): the Canny workspace, sized on first use
         self.enc_plans = {}           # (B, H, W) -> _EncPlan: the encoder stage of image-to-image requests
         self.var_h = self.var_d = None         # variations (generate(variation=)): pinned / device staging of sub and base, sized on first use
+        # SD upscale (backends/sdupscale.py): the decoded tiles of the request in flight, the combined picture and its pinned
+        # read-back buffer; sized on first use, grown on demand
+        self.grid_tiles = self.grid_out = self.h_grid = None
 
 
 class _Plan:
@@ -398,7 +401,7 @@ class LcmHipPipeline:
 
     @torch.inference_mode()
     def generate_img2img(self, prompt_embeds, seeds, images_u8, width, height, steps, strength, guidance_scale=1.0,
-                         negative_embeds=None, want_float=False, noises=None, lane=0, sampler=None):
+                         negative_embeds=None, want_float=False, noises=None, lane=0, sampler=None, tiles=None):
         """Image-to-image with the semantics of diffusers' LatentConsistencyModelImg2ImgPipeline: images_u8 uint8 [B,H,W,3] at the
         request's size -> AutoencoderKL encoder -> z = (mean + exp(0.5 clamp(logvar, -30, 20)) e0) scaling_factor -> re-noised to
         the first timestep of ``timesteps(steps, strength)`` with e1 -> ``steps`` LCM steps over that schedule -> decode.  The
@@ -410,7 +413,10 @@ class LcmHipPipeline:
         sampler = (name, "normal" | "karras") (samplers.py): the tail of that sampler's ``steps``-step schedule the strength leaves
         (``samplers.img2img_tables``) in place of the LCM pass, from z re-noised to the tail's first noise level with e1 by the same
         hand-over launch; the LCM bound on steps x strength does not apply.  The draws are the same; ``unet_evals`` counts the
-        tail's evaluations."""
+        tail's evaluations.
+        tiles = (store, k0, n): the pass serves tiles k0 .. k0 + n - 1 of an SD-upscale request (``grid_store``): the decoded
+        pictures of its first n slots are copied device-to-device into the store behind the read-backs, on the lane's stream, and
+        are not read back: the result's ``rgb`` is None."""
         torch.cuda.set_device(self.device)
         pe = torch.as_tensor(prompt_embeds)
         B = pe.shape[0]
@@ -453,8 +459,19 @@ class LcmHipPipeline:
                                       self.vae.cfg["scaling_factor"], nsa, nsb, P.xk[0], P.lat, B, h, w,
                                       moments=E.moments if want_float else None, dup=do_cfg)
 
-        out, _ = self._request([P], pe, negative_embeds, guidance_scale, upload, front, want_float=want_float,
-                               more=lambda: E.h_z.copy_(P.xk[0], non_blocking=True))
+        def more():
+            E.h_z.copy_(P.xk[0], non_blocking=True)
+            if tiles is not None:
+                store, k0, n = tiles
+                store[k0:k0 + n].copy_(P.rgb[:n], non_blocking=True)
+
+        if tiles is not None:
+            store, k0, n = tiles
+            if (store.dtype != torch.uint8 or tuple(store.shape[1:]) != (height, width, 3) or not 1 <= n <= B
+                    or not 0 <= k0 <= store.shape[0] - n):
+                raise LcmHipError(f"tiles {k0} .. {k0 + n - 1} of a pass of {B} do not fit a store of {tuple(store.shape)} {store.dtype}")
+        out, _ = self._request([P], pe, negative_embeds, guidance_scale, upload, front, want_float=want_float, more=more,
+                               read_rgb=tiles is None)
         out.update(init_latents=E.h_z.numpy().copy(),
                    unet_evals=(steps if sampler is None else len(P.sampler.ts)) * (2 if do_cfg else 1))
         if want_float:
@@ -945,12 +962,13 @@ class LcmHipPipeline:
             P.graph.launch()
 
     def _request(self, plans, pe, negative_embeds, guidance_scale, upload=None, front=None, want_float=False, taps=None, more=None,
-                 vary=None):
+                 vary=None, read_rgb=True):
         """The one sequence of every request kind, on the lane's stream.  plans: every plan of the request, the last one gives
         the picture; their pinned staging (h_lat, h_noise) is filled.  upload(): the kind's own uploads (hint, picture, start
         latents, SDXL rows); vary(): a variation's upload and its one launch into the first plan's lat0 (``_stage_variation``; None
         for every request without one); front(eager): the stage ahead of the last plan and its hand-over launch; more():
-        device-side copies to queue after the read-backs -> (base result dict, what more() returned).  The rules:
+        device-side copies to queue after the read-backs -> (base result dict, what more() returned).  read_rgb=False: the decoded
+        pictures stay on the device (an SD-upscale pass: more() keeps them in the tile store) and the dict's "rgb" is None.  The rules:
           * noise is drawn on the host, by the caller, before anything is launched: the graphs are RNG-free;
           * the graphs of EVERY plan of the request are ensured before its uploads: a warm-up pass overwrites plan state;
           * eager launches (use_graph=False, want_float, taps) hold _build_lock: they allocate scratch;
@@ -975,12 +993,13 @@ class LcmHipPipeline:
             if front is not None:
                 front(eager)
             self._run_plan(P, guidance_scale, eager, want_float, taps)
-            P.h_rgb.copy_(P.rgb, non_blocking=True)
+            if read_rgb:
+                P.h_rgb.copy_(P.rgb, non_blocking=True)
             P.h_pool8.copy_(P.pool8, non_blocking=True)
             P.h_latout.copy_(P.lat[P.B:] if P.do_cfg else P.lat, non_blocking=True)
             extra = more() if more is not None else None
             stream.synchronize()
-        out = dict(rgb=P.h_rgb.numpy().copy(), latents=P.h_latout.numpy().copy(), pool8=P.h_pool8.numpy().copy())
+        out = dict(rgb=P.h_rgb.numpy().copy() if read_rgb else None, latents=P.h_latout.numpy().copy(), pool8=P.h_pool8.numpy().copy())
         if want_float:
             out["image"] = P.img_f32.cpu().numpy()       # NHWC float, pre-clamp
         return out, extra
@@ -1232,9 +1251,12 @@ class LcmHipPipeline:
         """The uploads that came at another size, on the current (the lane's) stream, outside any captured graph: per picture the
         raw upload into the lane's source buffer, then the Lanczos resampler (include/lcm_hip.h; csrc/resize.hip) straight into
         slot b of dst ([B,H,W,3] or [B,H,W]).  Source buffer and workspace belong to the lane and grow on demand; they are
-        allocated on this stream, which orders every reuse behind the launches that read them.  Nothing is read back."""
+        allocated on this stream, which orders every reuse behind the launches that read them.  Nothing is read back.
+        Neighbouring entries that hold the same ``pixels`` object (the tiles of an SD-upscale request: windows of one grid of
+        one picture) share one upload: the source buffer still holds it."""
         if not fits:
             return
+        held = None                                      # the pixels object L.fit_src holds
         for b, f in enumerate(fits):
             if f is None:
                 continue
@@ -1242,8 +1264,11 @@ class LcmHipPipeline:
             n = a.numel()
             if L.fit_src is None or L.fit_src.numel() < n:
                 L.fit_src = torch.empty(n, dtype=torch.uint8, device=self.device)
+                held = None
             src = L.fit_src[:n].view(a.shape)
-            src.copy_(a, non_blocking=True)
+            if f.pixels is not held:
+                src.copy_(a, non_blocking=True)
+                held = f.pixels
             sh, sw = a.shape[:2]
             win = (f.x0, f.y0, f.width, f.height)
             need = ops.resize_ws_bytes(sw, sh, 1 if a.dim() == 2 else 3, f.fit_w, f.fit_h, win)
@@ -1252,6 +1277,41 @@ class LcmHipPipeline:
             if L.fit_ws is None or L.fit_ws.numel() < need:
                 L.fit_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             ops.resize_lanczos_u8(src, dst[b], L.fit_ws, f.fit_w, f.fit_h, win)
+
+    def grid_store(self, lane, n_tiles, tile_h, tile_w):
+        """The lane's tile store of an SD-upscale request: uint8 [n_tiles, tile_h, tile_w, 3] on the device, a view of a buffer
+        that belongs to the lane, grows on demand and is allocated on the lane's stream (like the resampler's source buffer:
+        every reuse is ordered behind the launches that read it).  ``generate_img2img(tiles=)`` fills it pass by pass."""
+        L = self.lane(lane)
+        n = int(n_tiles) * int(tile_h) * int(tile_w) * 3
+        if not 0 < n < 1 << 31:
+            raise LcmHipError(f"{n_tiles} tiles of {tile_w}x{tile_h} are outside the combine launch's domain (2^31 bytes)")
+        if L.grid_tiles is None or L.grid_tiles.numel() < n:
+            with torch.cuda.stream(L.stream):
+                L.grid_tiles = torch.empty(n, dtype=torch.uint8, device=self.device)
+        return L.grid_tiles[:n].view(int(n_tiles), int(tile_h), int(tile_w), 3)
+
+    @torch.inference_mode()
+    def combine_grid(self, lane, store, W, H, overlap, xs, ys):
+        """The tiles of ``store`` (``grid_store``; tile r * cols + c at (xs[c], ys[r])) -> the W x H picture, uint8 [H, W, 3] on
+        the host: one launch of lcm_grid_combine_rgb8 on the lane's stream (include/lcm_hip.h defines the bytes), one
+        device-to-host copy, one synchronize.  No tile pixel travels to the host for it."""
+        torch.cuda.set_device(self.device)
+        L = self.lane(lane)
+        th, tw = int(store.shape[1]), int(store.shape[2])
+        desc = ops.grid_desc(W, H, tw, th, overlap, xs, ys)
+        if store.shape[0] != desc.rows * desc.cols:
+            raise LcmHipError(f"a grid of {desc.cols} x {desc.rows} tiles and a store of {store.shape[0]}")
+        n = int(W) * int(H) * 3
+        with torch.cuda.stream(L.stream):
+            if L.grid_out is None or L.grid_out.numel() < n:
+                L.grid_out = torch.empty(n, dtype=torch.uint8, device=self.device)
+                L.h_grid = torch.empty(n, dtype=torch.uint8).pin_memory()
+            out, host = L.grid_out[:n], L.h_grid[:n]
+            ops.grid_combine_rgb8(store, out, desc)
+            host.copy_(out, non_blocking=True)
+            L.stream.synchronize()
+        return host.numpy().reshape(int(H), int(W), 3).copy()
 
     def _stage_variation(self, P: _Plan, variation, B, h, w):
         """The variations of a batch (``generate``'s variation=) -> None when no slot has one, else vary(): called on the lane's
