@@ -33,9 +33,25 @@ struct HaloParams {
     int H, W;               // logical (post-upsample) image size == output size
     int tiles_y, tiles_x;
     int staged_epi;         // 1: residual in / result out through an LDS image of the tile, whole rows (tile_epilogue_staged)
+    FastDiv fd_per_img, fd_tiles_x;      // m-tile -> (image, tile row, tile column) without a run-time division (halo_derive)
 };
 
+static inline void halo_derive(HaloParams& hp) {
+    igemm_derive(hp.g);
+    hp.fd_per_img = fastdiv_make(hp.tiles_y * hp.tiles_x);
+    hp.fd_tiles_x = fastdiv_make(hp.tiles_x);
+}
+
 static __device__ __attribute__((aligned(256))) half_t g_zero_page_h[128];
+
+// Everything the path to the first halo DMA reads, asked for in one batch of scalar loads with one wait at kernel entry; left
+// to the compiler they come in five dependent batches, each waited for before the next is issued.
+#define HALO_ENTRY_ARGS(hp)                                                                                                  \
+    asm volatile("" ::"s"((hp).g.A), "s"((hp).g.A2), "s"((hp).g.W), "s"((hp).g.N), "s"((hp).g.K), "s"((hp).g.Cin), "s"((hp).C1), \
+                 "s"((hp).g.Hin), "s"((hp).g.Win), "s"((hp).g.ups), "s"((hp).H), "s"((hp).W), "s"((hp).g.mtiles),            \
+                 "s"((hp).g.ntiles), "s"((hp).tiles_y), "s"((hp).tiles_x), "s"((hp).g.fd_ntiles.mul), "s"((hp).g.fd_ntiles.shr), \
+                 "s"((hp).fd_per_img.mul), "s"((hp).fd_per_img.shr), "s"((hp).fd_tiles_x.mul), "s"((hp).fd_tiles_x.shr),     \
+                 "s"((hp).g.fd_splits.mul), "s"((hp).g.fd_splits.shr))
 
 // Canonical GroupNorm-statistics slabs of a convolution output (see igemm_epilogue): a slab is the 32-pixel patch
 // (32/TW rows x TW columns, TW fixed by the image width) that one fragment pair of a wave covers, indexed by its
@@ -73,20 +89,25 @@ __global__ __launch_bounds__(256, PF ? 2 : 3) void conv_halo_kernel(HaloParams h
     char* wsm = smem + XBYTES;
 
     const IgemmParams& p = hp.g;
+    HALO_ENTRY_ARGS(hp);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave & 1, wn = wave >> 1;
     const int tile = xcd_remap(blockIdx.x, p.mtiles * p.ntiles);
-    const int mt4 = tile / p.ntiles, nt = tile - mt4 * p.ntiles;
+    const int mt4 = fastdiv(tile, p.fd_ntiles), nt = tile - mt4 * p.ntiles;
     const int phase = PH ? (mt4 & 3) : 0, mt = PH ? (mt4 >> 2) : mt4;
     const int py = phase >> 1, px = phase & 1;
     const int IH = PH ? p.Hin : hp.H, IW = PH ? p.Win : hp.W;      // image the halo is cut from
     const int per_img = hp.tiles_y * hp.tiles_x;
-    const int bimg = mt / per_img, tr = mt - bimg * per_img;
-    const int ty = tr / hp.tiles_x, tx = tr - ty * hp.tiles_x;
+    const int bimg = fastdiv(mt, hp.fd_per_img), tr = mt - bimg * per_img;
+    const int ty = fastdiv(tr, hp.fd_tiles_x), tx = tr - ty * hp.tiles_x;
     const int y0 = ty * TH, x0 = tx * TW;
     const int n_base = nt * BN;
     const int C2 = p.Cin - hp.C1;
+    // the zero page's address once, in scalar registers for the whole kernel: left to itself the compiler fetches it from the
+    // global offset table again at every DMA site, a scalar load and its wait in front of each issue
+    const half_t* zero_page = g_zero_page_h;
+    asm volatile("" : "+s"(zero_page));
 
     // ---- per-thread halo vector descriptors (constant over the K loop) ----
     int h_pix[NV];       // physical pixel index (b*Hin + py)*Win + px, or -1 (zero fill)
@@ -123,8 +144,8 @@ __global__ __launch_bounds__(256, PF ? 2 : 3) void conv_halo_kernel(HaloParams h
         for (int b = 0; b < TM; ++b) acc[a][b] = (f4){0.f, 0.f, 0.f, 0.f};
 
     const int nchunks = p.Cin >> 6;
-    const int c_begin = (int)((long long)blockIdx.y * nchunks / p.splits);
-    const int c_end = (int)((long long)(blockIdx.y + 1) * nchunks / p.splits);
+    int c_begin, c_end;
+    split_bounds(blockIdx.y, nchunks, p.fd_splits, c_begin, c_end);
     bool first = true;
 
     // XFORM: the raw halo of chunk c+1 is fetched into registers while the 9 taps of chunk c run (issued behind the barrier
@@ -188,7 +209,7 @@ __global__ __launch_bounds__(256, PF ? 2 : 3) void conv_halo_kernel(HaloParams h
                             const int hr = (tid + 256 * i) >> 3;
                             const half_t* src = h_pix[i] >= 0
                                 ? src_base + (long long)h_pix[i] * src_ld + src_c + ((pos ^ (hr & 7)) << 3)
-                                : g_zero_page_h;
+                                : zero_page;
                             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                                              (__attribute__((address_space(3))) void*)(xs + (wave + 4 * i) * 1024),
                                                              16, 0, 0);
@@ -284,20 +305,25 @@ __global__ __launch_bounds__(256, 2) void conv_halo_pipe_kernel(HaloParams hp) {
     char* wsm0 = smem + 2 * XBYTES;        // WS weight-step buffers (TPS tap slices each)
 
     const IgemmParams& p = hp.g;
+    HALO_ENTRY_ARGS(hp);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave & 1, wn = wave >> 1;
     const int tile = xcd_remap(blockIdx.x, p.mtiles * p.ntiles);
-    const int mt4 = tile / p.ntiles, nt = tile - mt4 * p.ntiles;
+    const int mt4 = fastdiv(tile, p.fd_ntiles), nt = tile - mt4 * p.ntiles;
     const int phase = PH ? (mt4 & 3) : 0, mt = PH ? (mt4 >> 2) : mt4;
     const int py = phase >> 1, px = phase & 1;
     const int IH = PH ? p.Hin : hp.H, IW = PH ? p.Win : hp.W;      // image the halo is cut from
     const int per_img = hp.tiles_y * hp.tiles_x;
-    const int bimg = mt / per_img, tr = mt - bimg * per_img;
-    const int ty = tr / hp.tiles_x, tx = tr - ty * hp.tiles_x;
+    const int bimg = fastdiv(mt, hp.fd_per_img), tr = mt - bimg * per_img;
+    const int ty = fastdiv(tr, hp.fd_tiles_x), tx = tr - ty * hp.tiles_x;
     const int y0 = ty * TH, x0 = tx * TW;
     const int n_base = nt * BN;
     const int C2 = p.Cin - hp.C1;
+    // the zero page's address once, in scalar registers for the whole kernel: left to itself the compiler fetches it from the
+    // global offset table again at every DMA site, a scalar load and its wait in front of each issue
+    const half_t* zero_page = g_zero_page_h;
+    asm volatile("" : "+s"(zero_page));
 
     int h_pix[NV];
     const int pos = tid & 7;
@@ -326,8 +352,8 @@ __global__ __launch_bounds__(256, 2) void conv_halo_pipe_kernel(HaloParams hp) {
         for (int b = 0; b < TM; ++b) acc[a][b] = (f4){0.f, 0.f, 0.f, 0.f};
 
     const int nchunks = p.Cin >> 6;
-    const int c_begin = (int)((long long)blockIdx.y * nchunks / p.splits);
-    const int c_end = (int)((long long)(blockIdx.y + 1) * nchunks / p.splits);
+    int c_begin, c_end;
+    split_bounds(blockIdx.y, nchunks, p.fd_splits, c_begin, c_end);
     const int T = (c_end - c_begin) * G;
 
     auto issue_halo = [&](int c64, int hb) {
@@ -343,7 +369,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo_pipe_kernel(HaloParams hp) {
                 const int hr = (tid + 256 * i) >> 3;
                 const half_t* src = h_pix[i] >= 0
                     ? src_base + (long long)h_pix[i] * src_ld + src_c + ((pos ^ (hr & 7)) << 3)
-                    : g_zero_page_h;
+                    : zero_page;
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                                  (__attribute__((address_space(3))) void*)(xs + (wave + 4 * i) * 1024), 16, 0, 0);
             }
@@ -375,7 +401,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo_pipe_kernel(HaloParams hp) {
         for (int a = 0; a < TN; ++a)
 #pragma unroll
             for (int b = 0; b < TM; ++b) tot[a][b] = (f4){0.f, 0.f, 0.f, 0.f};
-        plen = (int)((long long)nchunks / p.seg_parts) * G;
+        plen = fastdiv(nchunks, p.fd_seg) * G;
     }
     int wb = 0;
     constexpr int LPS = RW * TPS;          // LDS-DMA instructions per thread per K-step
@@ -465,7 +491,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo_pipe_kernel(HaloParams hp) {
                         acc[a][b] = (f4){0.f, 0.f, 0.f, 0.f};
                     }
                 ++part;
-                plen = ((int)((long long)(part + 1) * nchunks / p.seg_parts) - (int)((long long)part * nchunks / p.seg_parts)) * G;
+                plen = (fastdiv((part + 1) * nchunks, p.fd_seg) - fastdiv(part * nchunks, p.fd_seg)) * G;
             }
         }
     }
@@ -513,6 +539,7 @@ static void launch_halo(HaloParams& hp, hipStream_t s, int force) {     // force
     hp.tiles_y = ((PH ? hp.g.Hin : hp.H) + TH - 1) / TH;
     hp.tiles_x = ((PH ? hp.g.Win : hp.W) + TW - 1) / TW;
     hp.g.ntiles = hp.g.N / BN;
+    halo_derive(hp);
     dim3 grid(hp.g.mtiles * hp.g.ntiles, hp.g.splits, 1);
     if constexpr (!XFORM) if (hp.g.seg_parts > 1) {     // segmented accumulation: the pipelined kernel (2 workgroups per CU: room for `tot`)
         // (a kernel row of taps per step double-buffers its fragments in registers: with the second accumulator set that only
@@ -605,6 +632,7 @@ static void launch_halo_narrow(HaloParams& hp, hipStream_t s, int force) {
     hp.tiles_y = (hp.H + TH - 1) / TH;
     hp.tiles_x = (hp.W + TW - 1) / TW;
     hp.g.ntiles = hp.g.N / BN;
+    halo_derive(hp);
     dim3 grid(hp.g.mtiles * hp.g.ntiles, hp.g.splits, 1);
     char nm[64];
     if (force == 3) {

@@ -211,9 +211,17 @@ __global__ __launch_bounds__(256, S == 1 ? (BM + BN < 256 ? 4 : 3) : 2) void ige
     const int wm = wave & 1, wn = wave >> 1;
     // A workgroup walks n_iters consecutive n-tiles of one m-tile; the (n-tile, k-tile) steps are flattened so the
     // LDS-DMA ring keeps flowing across n-tile boundaries (short-K GEMMs: no pipeline ramp / drain per tile).
-    const int ngroups = p.ntiles / p.n_iters;
+    // No run-time division in front of the first ring stage: the launcher derives ngroups and the magic numbers (fastdiv.h).
+    // Everything the path to the first stage reads is asked for here, in one batch of scalar loads with one wait; left to the
+    // compiler the second half of them is issued ~200 instructions in, behind the first wait, and waited for again.
+    // (the single-buffer form runs at the 128-VGPR budget of four workgroups per CU and has other workgroups to hide behind)
+    if constexpr (S >= 2)
+    asm volatile("" ::"s"(p.A), "s"(p.A2), "s"(p.W), "s"(p.M), "s"(p.K), "s"(p.lda), "s"(p.lda2), "s"(p.K1), "s"(p.strideA),
+                 "s"(p.strideW), "s"(p.mtiles), "s"(p.n_iters), "s"(p.ngroups), "s"(p.fd_ngroups.mul), "s"(p.fd_ngroups.shr),
+                 "s"(p.fd_splits.mul), "s"(p.fd_splits.shr));
+    const int ngroups = p.ngroups;
     const int tile = xcd_remap(blockIdx.x, p.mtiles * ngroups);
-    const int mt = tile / ngroups, nt0 = (tile - mt * ngroups) * p.n_iters;
+    const int mt = fastdiv(tile, p.fd_ngroups), nt0 = (tile - mt * ngroups) * p.n_iters;
     const int m_base = mt * BM;
     const int z = blockIdx.z;
 
@@ -235,21 +243,24 @@ __global__ __launch_bounds__(256, S == 1 ? (BM + BN < 256 ? 4 : 3) : 2) void ige
             a_off[i] = (long long)m;
         } else {
             const int hw = p.Hout * p.Wout;
-            const int b = m / hw, rem = m - b * hw;
-            const int oy = rem / p.Wout;
+            const int b = fastdiv(m, p.fd_hw), rem = m - b * hw;
+            const int oy = fastdiv(rem, p.fd_wout);
             a_b[i] = b; a_y[i] = oy * p.stride - 1; a_x[i] = (rem - oy * p.Wout) * p.stride - 1;
         }
     }
     const half_t* wptr = Wb + (long long)row0 * p.K + schunk;
     const int nk_all = p.K >> 6;
-    const int kt0 = (int)((long long)blockIdx.y * nk_all / p.splits);
-    const int kt1 = (int)((long long)(blockIdx.y + 1) * nk_all / p.splits);
+    int kt0, kt1;
+    split_bounds(blockIdx.y, nk_all, p.fd_splits, kt0, kt1);
     const int nkr = kt1 - kt0;
     const int T = nkr * p.n_iters;
 
-    auto issue_tile = [&](int t, int buf) {          // t = flattened (n-tile, k-tile) step
-        const int ni = t / nkr;
-        const int kt = kt0 + (t - ni * nkr);
+    // The flattened (n-tile, k-tile) steps are issued in order, one per call: the step's coordinates are counters.
+    WrapCounter iss = {kt0, 0};
+    auto issue_tile = [&](int buf) {
+        const int ni = iss.outer;
+        const int kt = iss.inner;
+        wrap_step(iss, kt0, kt1);
         const int n_base_i = (nt0 + ni) * BN;
         char* xs = smem + buf * BUF + wave * 8 * 128;
         char* ws = xs + XBYTES;
@@ -267,7 +278,7 @@ __global__ __launch_bounds__(256, S == 1 ? (BM + BN < 256 ? 4 : 3) : 2) void ige
             }
         } else {
             const int cpt = p.Cin >> 6;
-            const int tap = kt / cpt;
+            const int tap = fastdiv(kt, p.fd_cpt);
             const int c0 = ((kt - tap * cpt) << 6) + schunk;
             const int dy = tap / 3, dx = tap - dy * 3;
             const int Hl = p.ups ? p.Hin * 2 : p.Hin, Wl = p.ups ? p.Win * 2 : p.Win;
@@ -307,7 +318,7 @@ __global__ __launch_bounds__(256, S == 1 ? (BM + BN < 256 ? 4 : 3) : 2) void ige
 
 #pragma unroll
     for (int s = 0; s < S - 1; ++s)
-        if (s < T) issue_tile(s, s);
+        if (s < T) issue_tile(s);
     const __attribute__((address_space(3))) float* ln_lds = nullptr;
     if constexpr (ln) {       // this n-tile's ln_g | ln_c into LDS (behind the ring's stages), outside the K loop and under
                               // the latency of the first tiles just issued
@@ -324,7 +335,7 @@ __global__ __launch_bounds__(256, S == 1 ? (BM + BN < 256 ? 4 : 3) : 2) void ige
         for (int a = 0; a < TN; ++a)
 #pragma unroll
             for (int b = 0; b < TM; ++b) tot[a][b] = (f4){0.f, 0.f, 0.f, 0.f};
-        nkp = (int)((long long)nk_all / p.seg_parts);          // part 0 = k-tiles [0, nk_all / parts)
+        nkp = fastdiv(nk_all, p.fd_seg);          // part 0 = k-tiles [0, nk_all / parts)
     }
     int buf = 0, kstep = 0, ni_cur = 0;
     for (int t = 0; t < T; ++t) {
@@ -332,7 +343,7 @@ __global__ __launch_bounds__(256, S == 1 ? (BM + BN < 256 ? 4 : 3) : 2) void ige
         const int newer = T - 1 - t;
         if (S == 1) {   // single LDS buffer: rely on 4-5 co-resident workgroups per CU to cover the load latency
             if (t > 0) __builtin_amdgcn_s_barrier();      // everyone done reading the previous tile
-            issue_tile(t, 0);
+            issue_tile(0);
             wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
         } else {
@@ -342,7 +353,7 @@ __global__ __launch_bounds__(256, S == 1 ? (BM + BN < 256 ? 4 : 3) : 2) void ige
             else if (S >= 3 && newer >= 1) wait_vmcnt<(S >= 3 ? 1 : 0) * LPT>();
             else wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
-            if (t + S - 1 < T) issue_tile(t + S - 1, (buf + S - 1) % S);
+            if (t + S - 1 < T) issue_tile((buf + S - 1) % S);
         }
 
         const char* xs = smem + buf * BUF + (wm * (BM / 2)) * 128;
@@ -384,7 +395,7 @@ __global__ __launch_bounds__(256, S == 1 ? (BM + BN < 256 ? 4 : 3) : 2) void ige
                         acc[a][b] = (f4){0.f, 0.f, 0.f, 0.f};
                     }
                 ++part;
-                nkp = (int)((long long)(part + 1) * nk_all / p.seg_parts) - (int)((long long)part * nk_all / p.seg_parts);
+                nkp = fastdiv((part + 1) * nk_all, p.fd_seg) - fastdiv(part * nk_all, p.fd_seg);
             }
             continue;
         }
@@ -445,14 +456,13 @@ __device__ __forceinline__ int reduce_pixel(const IgemmParams& p, int slab, int 
         const int m = slab * 32 + b * 16 + l;
         return m < p.M ? m : -1;
     }
-    const int TW = p.rg_kind == 1 ? 16 : 8, RS = 32 / TW;
-    const int sx = (p.rg_IW + TW - 1) / TW, sy = (p.rg_IH + RS - 1) / RS;
+    const int twl = p.rg_tw_log2, sx = p.rg_sx;          // patch width 16 or 8 (a shift), patches per image row
     int phase = 0;
     if (p.rg_ph) { phase = slab & 3; slab >>= 2; }
-    const int bimg = slab / (sy * sx), r = slab - bimg * (sy * sx);
-    const int syi = r / sx, sxi = r - syi * sx;
-    const int q = b * 16 + l;                          // pixel of the slab, row-major over its RS x TW patch
-    const int y = syi * RS + q / TW, x = sxi * TW + q % TW;
+    const int bimg = fastdiv(slab, p.fd_rg_img), r = slab - bimg * p.rg_img;
+    const int syi = fastdiv(r, p.fd_rg_sx), sxi = r - syi * sx;
+    const int q = b * 16 + l;                          // pixel of the slab, row-major over its (32 >> twl) x (1 << twl) patch
+    const int y = (syi << (5 - twl)) + (q >> twl), x = (sxi << twl) + (q & ((1 << twl) - 1));
     if (y >= p.rg_IH || x >= p.rg_IW) return -1;
     if (p.rg_ph) return (bimg * p.rg_OH + 2 * y + (phase >> 1)) * p.rg_OW + 2 * x + (phase & 1);
     return (bimg * p.rg_OH + y) * p.rg_OW + x;
@@ -468,9 +478,13 @@ __device__ __forceinline__ int reduce_pixel(const IgemmParams& p, int slab, int 
 #define RED_BATCH 8
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(IgemmParams p, int total_slabs) {
 #pragma clang fp contract(off)
+    // one batch of scalar loads, one wait, for everything in front of the slab loads (see igemm2_kernel)
+    asm volatile("" ::"s"(p.ws), "s"(p.M), "s"(p.N), "s"(p.splits), "s"(total_slabs), "s"(p.fd_ncg.mul), "s"(p.fd_ncg.shr),
+                 "s"(p.rg_kind), "s"(p.rg_ph), "s"(p.rg_IH), "s"(p.rg_IW), "s"(p.rg_OH), "s"(p.rg_OW), "s"(p.rg_sx), "s"(p.rg_img),
+                 "s"(p.rg_tw_log2), "s"(p.fd_rg_img.mul), "s"(p.fd_rg_img.shr), "s"(p.fd_rg_sx.mul), "s"(p.fd_rg_sx.shr));
     const int lane = threadIdx.x & 63, ncg = p.N >> 4;
-    const long long wv = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int slab = (int)(wv / ncg), cg = (int)(wv - (long long)slab * ncg);
+    const int wv = blockIdx.x * 4 + (threadIdx.x >> 6);          // (< 2^31: the fp32 slabs behind 2^31 waves would be terabytes)
+    const int slab = fastdiv(wv, p.fd_ncg), cg = wv - slab * ncg;
     if (slab >= total_slabs) return;
     const int l = lane & 15, fq = lane >> 4;
     const int n = cg * 16 + fq * 4;
@@ -496,7 +510,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(IgemmParams p, int t
     if (p.bias) hb = *reinterpret_cast<const h4*>(p.bias + n);
     if (p.rowadd) {
 #pragma unroll
-        for (int b = 0; b < 2; ++b) ha[b] = *reinterpret_cast<const h4*>(p.rowadd + (long long)(m[b] / p.rows_per_batch) * p.ld_rowadd + n);
+        for (int b = 0; b < 2; ++b) ha[b] = *reinterpret_cast<const h4*>(p.rowadd + (long long)fastdiv(m[b], p.fd_rpb) * p.ld_rowadd + n);
     }
     if (p.res) {
 #pragma unroll
@@ -607,6 +621,7 @@ int lcm_total_slabs(const IgemmParams& p) {
 void lcm_launch_splitk_reduce(IgemmParams& p, hipStream_t s) {
     const int total = lcm_total_slabs(p);
     const long long waves = (long long)total * (p.N >> 4);
+    igemm_derive(p);
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, p, total);
 }
 
@@ -805,6 +820,7 @@ static int launch_v2(IgemmParams& p, dim3 grid, hipStream_t s) {
     constexpr int smem = S * (BM + BN) * 128 + (LN ? 2 * BN * 4 : 0);       // LN: + this n-tile's ln_g | ln_c
     // the staged epilogue: a plain launch with a residual tile to fetch, the tile image fits the ring, strided z-batches excluded
     constexpr bool can_stage = MODE == 0 && !LN && !SEG && BN >= 64 && S * (BM + BN) * 128 >= BM * BN * 2;
+    igemm_derive(p);
     if constexpr (can_stage) if (g_staged_epi_gemm && p.res && p.splits == 1 && p.n_iters == 1 && p.epi == 0 && grid.z == 1) {
         static LcmDevOnce attr_once_e;
         if (auto once_guard = attr_once_e.first()) {
@@ -1060,6 +1076,7 @@ struct HaloParams {
     int H, W;
     int tiles_y, tiles_x;
     int staged_epi;
+    FastDiv fd_per_img, fd_tiles_x;
 };
 int lcm_conv_halo_launch(HaloParams& hp, int B, hipStream_t s, int* slabs_per_image);
 

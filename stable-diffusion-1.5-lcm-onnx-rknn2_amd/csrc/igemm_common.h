@@ -2,6 +2,7 @@
 // tile remap, and the common epilogue (split-K slab store | bias + row add + scale + residual | GEGLU).
 #pragma once
 #include "common.h"
+#include "fastdiv.h"
 
 struct IgemmParams {
     const half_t* A;
@@ -40,7 +41,39 @@ struct IgemmParams {
     float ln_eps;
     int n_iters;         // igemm2: consecutive n-tiles one workgroup walks with a continuous LDS-DMA pipeline (>= 1)
     long long stats_cap; // host side: bytes the caller allocated behind `stats` (the launch is refused when the slabs do not fit)
+    // Launch-time constants the kernels used to derive by dividing in front of their first load (igemm_derive fills them
+    // from the fields above right before a launch; fastdiv.h).
+    int ngroups;         // igemm2: ntiles / n_iters, the n-tile groups of one m-tile
+    FastDiv fd_ngroups;  // tile -> (m-tile, group)
+    FastDiv fd_ntiles;   // halo convs: tile -> (m-tile, n-tile)
+    FastDiv fd_splits;   // blockIdx.y's k-tile (chunk) range
+    FastDiv fd_hw, fd_wout, fd_cpt;      // row-gather 3x3 (MODE 1): row -> (image, y, x); k-tile -> tap
+    FastDiv fd_seg;      // segmented accumulation: part bounds
+    // split-K reduce: wave -> (slab, channel group); slab -> (image, patch row, patch column)
+    int rg_sx, rg_img, rg_tw_log2;     // patches per image row / per image, log2 of the patch width
+    FastDiv fd_ncg, fd_rg_img, fd_rg_sx, fd_rpb;
 };
+
+// everything above that is a function of the launch's other fields
+inline void igemm_derive(IgemmParams& p) {
+    if (p.n_iters < 1) p.n_iters = 1;
+    p.ngroups = p.ntiles / p.n_iters;
+    p.fd_ngroups = fastdiv_make(p.ngroups);
+    p.fd_ntiles = fastdiv_make(p.ntiles);
+    p.fd_splits = fastdiv_make(p.splits);
+    p.fd_hw = fastdiv_make(p.Hout * p.Wout);
+    p.fd_wout = fastdiv_make(p.Wout);
+    p.fd_cpt = fastdiv_make(p.Cin >> 6);
+    p.fd_seg = fastdiv_make(p.seg_parts);
+    p.fd_ncg = fastdiv_make(p.N >> 4);
+    p.fd_rpb = fastdiv_make(p.rows_per_batch);
+    p.rg_tw_log2 = p.rg_kind == 1 ? 4 : 3;
+    const int TW = 1 << p.rg_tw_log2, RS = 32 / TW;
+    p.rg_sx = (p.rg_IW + TW - 1) / TW;
+    p.fd_rg_sx = fastdiv_make(p.rg_sx);
+    p.rg_img = ((p.rg_IH + RS - 1) / RS) * p.rg_sx;
+    p.fd_rg_img = fastdiv_make(p.rg_img);
+}
 
 // fused-statistics bounds check shared by the contraction entry points: slabs_per_image x images x N x (sum, sumsq) fp32
 #define LCM_STATS_FIT(p, slabs, images, what)                                                                              \
@@ -334,12 +367,14 @@ __device__ __forceinline__ void tile_epilogue_staged(const IgemmParams& p, f4 (&
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     __syncthreads();                              // every wave is done with the K loop's LDS tiles
     if (p.res) {
+        const half_t* zero_page = g_zero_page_epi;      // its address once, not once per DMA site (see conv_halo.hip)
+        asm volatile("" : "+s"(zero_page));
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             if ((wave + 4 * i) * 64 < PIECES) {   // wave-uniform: whole 1 KiB piece in range (PIECES is a multiple of 64)
                 const int v = tid + 256 * i, q = v / CH, cpos = v - q * CH;
                 const int m = row_of(q);
-                const half_t* src = m >= 0 ? p.res + (long long)m * p.ldr + n_base + stage_src<CH>(cpos, q) * 8 : g_zero_page_epi;
+                const half_t* src = m >= 0 ? p.res + (long long)m * p.ldr + n_base + stage_src<CH>(cpos, q) * 8 : zero_page;
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                                  (__attribute__((address_space(3))) void*)(stage + (wave + 4 * i) * 1024), 16, 0, 0);
             }

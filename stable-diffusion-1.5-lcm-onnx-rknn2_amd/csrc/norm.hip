@@ -12,6 +12,7 @@
 //   2. gn_finalize: one wave per (b, g): fixed-order reduction of the chunk partials -> mean, rstd
 //   3. gn_apply:    y = silu((x - mean) * rstd * gamma + beta), written as ONE concatenated tensor.
 #include "common.h"
+#include "fastdiv.h"
 
 #define GN_MAXC 2560
 #define GN_LDS_FLOATS 5120  // max(nrl * C, C) * 2
@@ -252,11 +253,15 @@ __global__ __launch_bounds__(256) void gn_from_stats_fused_kernel(const half_t* 
                                                                   const float* __restrict__ st1, int P1, const float* __restrict__ st2, int P2,
                                                                   const half_t* __restrict__ gamma, const half_t* __restrict__ beta,
                                                                   half_t* __restrict__ out, int HW, int groups, float inv_count, float eps,
-                                                                  int silu, int rows_per_wg) {
+                                                                  int silu, int rows_per_wg, int cpg, FastDiv fd_groups, FastDiv fd_hp) {
     __shared__ float red[8];
     __shared__ float sc_s[128], sh_s[128];
-    const int C = C1 + C2, cpg = C / groups;
-    const int bg = blockIdx.y, b = bg / groups, g = bg - b * groups, tid = threadIdx.x;
+    // cpg = C / groups and the two magic numbers (fastdiv.h) come from the launcher: no division chain in front of the
+    // first activation load.  Everything that path reads is asked for here, in one batch of scalar loads with one wait.
+    asm volatile("" ::"s"(x), "s"(x2), "s"(C1), "s"(C2), "s"(HW), "s"(groups), "s"(rows_per_wg), "s"(cpg), "s"(fd_groups.mul),
+                 "s"(fd_groups.shr), "s"(fd_hp.mul), "s"(fd_hp.shr));
+    const int C = C1 + C2;
+    const int bg = blockIdx.y, b = fastdiv(bg, fd_groups), g = bg - b * groups, tid = threadIdx.x;
     const int c_lo = g * cpg;
     // apply: work item = (pixel, channel pair of the group); consecutive threads take consecutive pairs of one pixel
     const int hp = cpg >> 1;
@@ -264,7 +269,7 @@ __global__ __launch_bounds__(256) void gn_from_stats_fused_kernel(const half_t* 
     const long long rowbase = (long long)b * HW;
     const int items = (r1 - r0) * hp;
     auto load_item = [&](int i) -> h2v {
-        const int pr = i / hp, j = i - pr * hp;
+        const int pr = fastdiv(i, fd_hp), j = i - pr * hp;
         const int c = c_lo + 2 * j;
         const long long row = rowbase + r0 + pr;
         const bool first = c < C1;
@@ -289,7 +294,7 @@ __global__ __launch_bounds__(256) void gn_from_stats_fused_kernel(const half_t* 
 #pragma unroll
     for (int k = 0; k < GN_PRE; ++k) asm volatile("" : "+v"(pre[k]));
     auto apply_store = [&](int i, h2v v) {
-        const int pr = i / hp, j = i - pr * hp;
+        const int pr = fastdiv(i, fd_hp), j = i - pr * hp;
         const int c = c_lo + 2 * j;
         const long long row = rowbase + r0 + pr;
         float f0 = __builtin_fmaf((float)v[0], sc_s[2 * j], sh_s[2 * j]), f1 = __builtin_fmaf((float)v[1], sc_s[2 * j + 1], sh_s[2 * j + 1]);
@@ -398,7 +403,7 @@ extern "C" int lcm_groupnorm_from_stats_f16(const void* x, int C1, const void* x
         hipLaunchKernelGGL(gn_from_stats_fused_kernel, dim3((HW + rows - 1) / rows, B * groups), dim3(256), 0, s,
                            (const half_t*)x, C1, (const half_t*)x2, C2, (const float*)stats1, P1, (const float*)stats2, P2,
                            (const half_t*)gamma, (const half_t*)beta, (half_t*)out, HW, groups,
-                           1.0f / ((float)HW * (float)cpg), eps, silu, rows);
+                           1.0f / ((float)HW * (float)cpg), eps, silu, rows, cpg, fastdiv_make(groups), fastdiv_make(cpg >> 1));
         LCM_CHECK_LAUNCH("gn_from_stats_fused");
         return LCM_OK;
     }

@@ -16,6 +16,6 @@ for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_
 done
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/pmc_${tag}_kt -- python3 "$@" > /dev/null 2>&1
 f=$(find gpurun_out/pmc_${tag}_kt -name "*kernel_stats.csv" | head -1)
-echo "== kernel stats" >> $out; head -6 "$f" >> $out
+echo "== kernel stats" >> $out; head -6 "$f" | grep -v "at::native" >> $out      # (the framework's fill kernels: names of 5 KB each)
 rm -rf gpurun_out/pmc_${tag}_kt
 cat $out
